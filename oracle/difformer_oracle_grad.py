@@ -16,6 +16,7 @@ All arithmetic runs in the dtype of the inputs; float64 is the yardstick of SURV
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -56,8 +57,12 @@ def gcn_conv(x, edge_index, edge_weight=None):
     n = x.shape[0]
     row, col = edge_index[0], edge_index[1]
     deg = torch.zeros(n, dtype=torch.float32).index_add_(0, col, torch.ones(col.shape[0], dtype=torch.float32))   # :66
-    d_in = (1.0 / deg[col]).sqrt()                                       # :67
-    d_out = (1.0 / deg[row]).sqrt()                                      # :68
+    # (1 / deg).sqrt() in float32, correctly rounded on every host: numpy's float32 divide and sqrt are IEEE-exact, torch's CPU
+    # kernels are one ulp off for some degrees on some CPUs -- and the golden fixtures hold the correctly rounded factors
+    with np.errstate(divide="ignore"):
+        inv_sqrt = torch.from_numpy(np.sqrt(np.float32(1.0) / deg.numpy()))
+    d_in = inv_sqrt[col]                                                 # :67
+    d_out = inv_sqrt[row]                                                # :68
     if edge_weight is None:
         value = torch.ones_like(row) * d_in * d_out                      # :71
     else:

@@ -8,7 +8,7 @@ R=$PWD; OUT=$R/gpurun_out/$T; mkdir -p $OUT
 set -x
 ./scripts/profile_c4.sh $T > $OUT/c4.log 2>&1
 for W in cifar15k-a-h300 stl13k-a-h400; do
-  python bench.py --workload $W --steps 30 --warmup 5 > $OUT/bench_$W.json 2> $OUT/bench_$W.err
+  python bench.py --workload $W --steps 30 --warmup 5 --full > $OUT/bench_$W.json 2> $OUT/bench_$W.err
   (cd /tmp; export TMPDIR=/tmp; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$W -o s -- python $R/bench.py --workload $W --steps 30 --warmup 5 --no-cpu-baseline --no-exact-pass > $OUT/stats_$W.log 2>&1)
   find $OUT/stats_$W -name "*kernel_stats.csv" -exec cp {} $OUT/${W}_kernel_stats.csv \;
 done

@@ -222,6 +222,26 @@ def test_bench_sharding_arithmetic_dry_run(world):
     assert one["parallelism"] == "single GPU" and one["n_local"] == 132534
 
 
+def test_bench_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an output within the budget is written whole; above it, the same seeded rows every call, with
+    their indices beside them, and every file float32 / float64 within the budget in all."""
+    import numpy as np
+    import bench
+    y = torch.randn(300, 7)
+    bench.dump_outputs(str(tmp_path / "whole"), y, 0, 1)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["output.npy"]
+    got = np.load(tmp_path / "whole" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 6000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), y, 1, 2)                 # rank 1 of 2: half the budget
+        assert sorted(os.listdir(tmp_path / d)) == ["output_rank1.npy", "output_sample_rows_rank1.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 3000
+    rows = np.load(tmp_path / "a" / "output_sample_rows_rank1.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "b" / "output_sample_rows_rank1.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "output_rank1.npy"), y.numpy()[rows.astype(np.int64)])
+
+
 def _train_worker(rank, world, port, kernel, n, heads, use_graph, out_q, product="row", hidden=16):
     for p in (ROOT, HERE):
         if p not in sys.path:

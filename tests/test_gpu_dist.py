@@ -160,7 +160,7 @@ def test_bench_with_two_ranks_runs_end_to_end(workload, product):
     env = dict(os.environ, DIFFORMER_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--workload", workload, "--shard-product", product]
+           "--workload", workload, "--shard-product", product, "--full"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -182,3 +182,27 @@ def test_bench_with_two_ranks_runs_end_to_end(workload, product):
         assert all(any(k.startswith("all_") for k in p["collectives_ms"]) for p in phases), phases
     else:
         assert d["scaling"] == "weak" and d["config"]["parallelism"] == "replicas x2"
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain single-GPU bench.py run prints the headline keys only (the --full measurements stay out of it), and
+    --dump-outputs writes the last timed forward: the same inputs every run, so two runs give the same outputs."""
+    import json
+    import subprocess
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--workload", "cora-s",
+               "--dump-outputs", str(tmp_path / d)]
+        res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, res.stdout[-2000:]
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 4 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["dtype"] == "f32"
+        assert rec["higher_is_better"] is True and rec["unit"] == "nodes/s"
+        assert not {"roofline", "cpu_baseline", "ms_per_step_exact_fp32", "ms_per_step_events", "cold_csr_build_ms"} & set(rec)
+        assert os.listdir(tmp_path / d) == ["output.npy"]
+        outs.append(np.load(tmp_path / d / "output.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (2708, 7) and np.isfinite(outs[0]).all()
+    assert np.allclose(outs[0], outs[1], rtol=1e-5, atol=1e-6 * float(np.abs(outs[0]).max()))
