@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DIFFORMER_HIP_LIB: another build of the SAME ABI (A/B kernel experiments); the default is the in-tree build
 LIB_PATH = os.environ.get("DIFFORMER_HIP_LIB") or os.path.join(_HERE, "lib", "libdifformer_hip.so")
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 c_i64, c_int, c_f32, c_vp, c_sz = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
@@ -87,8 +87,7 @@ SIGNATURES = {
     "dif_simple_coeffs_bwd_f32": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp,
                                           c_vp]),
     "dif_simple_layer_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp,
-                                     c_i64, c_int, c_f32, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
-                                     c_vp, c_sz, c_vp]),
+                                     c_i64, c_int, c_f32, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "dif_sliced_plan": (c_int, [c_i64, c_i64, c_int, c_vp]),
     "dif_sliced_measure": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp,
                                    c_vp, c_vp, c_vp, c_vp]),
@@ -98,9 +97,6 @@ SIGNATURES = {
     "dif_sliced_spmm_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp,
                                     c_i64, c_f32, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "dif_sliced_spmm_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
-    "dif_wide_partials": (c_i64, [c_int]),
-    "dif_wide_gram_f64": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp]),
-    "dif_wide_scale_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     "dif_row_order_workspace_bytes": (c_sz, [c_i64]),
     "dif_row_order": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "dif_simple_layer_head_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64,

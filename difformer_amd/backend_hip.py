@@ -832,9 +832,9 @@ class HipBackend:
 
     def simple_layer(self, x, coef, D, ax=None, Wv=None, bv=None, row_sums=None, gcn_scale=1.0, x0=None, residual=False,
                      alpha=0.5, ln_weight=None, ln_bias=None, eps=1e-5, relu=False, next_rowptr=None, next_plan=None,
-                     next_record=False, head=None, gather=None):
-        """-> out [n, D]; with next_plan -> (out, ys, record | None): also the slice-major scaled copy of `out` for the
-        next layer's SpMM (see gram()), and with next_record its Gram record from the same pass.
+                     head=None, gather=None):
+        """-> out [n, D]; with next_plan -> (out, ys): also the slice-major scaled copy of `out` for the next layer's SpMM
+        (see gram()).
         head = (Wo [Co, D], bo [Co]) float32, Co <= 128 (the model's output Linear, difformer.py:208): -> logits [n, Co]
         from the same pass; the layer's rows themselves are not stored.
         gather = (rowptr, src, val) of a one-block CSR over the same n nodes: the aggregation runs inside the layer kernel
@@ -842,7 +842,7 @@ class HipBackend:
         dev = _require_device(x, coef, ax, Wv, bv, row_sums, x0, ln_weight, ln_bias)
         if gather is not None:
             return self._simple_layer_gather(x, coef, D, gather, Wv, bv, gcn_scale, x0, residual, alpha, ln_weight, ln_bias,
-                                             eps, relu, head, ax is not None or next_plan is not None or next_record)
+                                             eps, relu, head, ax is not None or next_plan is not None)
         dt, sfx = _storage(x, ax, x0)              # activations: float32 or bfloat16; parameters always float32 here
         for t_, nm in ((coef, "coef"), (Wv, "Wv"), (bv, "bv"), (ln_weight, "ln_weight"), (ln_bias, "ln_bias"), (row_sums, "row_sums")):
             if t_ is not None:
@@ -863,7 +863,7 @@ class HipBackend:
         if head is not None:
             Wo, bo = (_f32(t_, "head").contiguous() for t_ in head)          # float32 (exact copies of bf16 parameters)
             Co = Wo.shape[0]
-            if next_plan is not None or next_record or Co > 128 or Wo.shape[1] != D:
+            if next_plan is not None or Co > 128 or Wo.shape[1] != D:
                 raise TypeError("difformer_amd: the fused output Linear needs Co <= 128 and no next-layer products")
             logits = torch.empty((n, Co), dtype=dt, device=dev)
             fn = self.lib.dif_simple_layer_head_bf16 if sfx == "bf16" else self.lib.dif_simple_layer_head_f32
@@ -876,10 +876,9 @@ class HipBackend:
             _lib.check(rc, "dif_simple_layer_head")
             return logits
         out = torch.empty((n, D), dtype=dt, device=dev)
-        record = ys = ws = None
-        ws_bytes = 0
+        ys = None
         if sfx == "bf16":
-            if next_plan is not None or next_record:
+            if next_plan is not None:
                 raise TypeError("difformer_amd: products for the next layer are float32-only")
             with _timed(self, "dif_simple_layer_f32", dev):
                 rc = self.lib.dif_simple_layer_bf16(_ptr(x), ldx, n, C, D, _ptr(coef), _ptr(ax), ldax, _ptr(Wv), _ptr(bv),
@@ -890,21 +889,14 @@ class HipBackend:
             return out
         if next_plan is not None:
             ys = torch.empty((D // 4, int(next_plan[6]) * int(next_plan[7]), 4), dtype=torch.float32, device=dev)
-        if next_record:
-            record = torch.empty(D * D + D + 2, dtype=torch.float32, device=dev)
-            ws_bytes = self.lib.dif_gram_workspace_bytes(n, D)
-            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         with _timed(self, "dif_simple_layer_f32", dev):
             rc = self.lib.dif_simple_layer_f32(_ptr(x), ldx, n, C, D, _ptr(coef), _ptr(ax), ldax, _ptr(Wv), _ptr(bv),
                                                _ptr(row_sums), float(gcn_scale), _ptr(x0), ldx0, int(bool(residual)),
                                                float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps), int(bool(relu)),
-                                               _ptr(out), D, _ptr(record), _ptr(next_rowptr) if ys is not None else None,
-                                               next_plan if ys is not None else None, _ptr(ys), _ptr(ws), ws_bytes,
-                                               _stream(dev))
+                                               _ptr(out), D, _ptr(next_rowptr) if ys is not None else None,
+                                               next_plan if ys is not None else None, _ptr(ys), _stream(dev))
         _lib.check(rc, "dif_simple_layer_f32")
-        if next_plan is None and not next_record:
-            return out
-        return out, ys, record
+        return out if next_plan is None else (out, ys)
 
     def _simple_layer_gather(self, x, coef, D, gather, Wv, bv, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
                              head, conflicting):
@@ -1209,16 +1201,6 @@ class HipBackend:
         _lib.check(rc, "dif_gram_sym_f32")
         return rec
 
-    def wide_gram(self, rec, C, n_global, S):
-        """Record of gram_sym -> (G~ float64 [(C+1), (C+1)], partial sums of the two norm products) -- dif_wide_gram_f64."""
-        dev = _require_device(rec, S)
-        Gt = torch.empty((C + 1, C + 1), dtype=torch.float64, device=dev)
-        partial = torch.empty(2 * self.lib.dif_wide_partials(C), dtype=torch.float64, device=dev)
-        with _timed(self, "dif_wide_gram_f64", dev):
-            rc = self.lib.dif_wide_gram_f64(_ptr(rec), C, int(n_global), _ptr(S), _ptr(Gt), _ptr(partial), _stream(dev))
-        _lib.check(rc, "dif_wide_gram_f64")
-        return Gt, partial
-
     def wide_coeffs(self, rec, C, n_global, S, V, P):
         """Record of gram_sym -> (B float32 [C, DV], bias float32 [DV]), the row GEMM's operands [Mn | u], [cn | cd]: both
         float64 products and their bookkeeping in two launches (dif_wide_coeffs_f64; no library GEMM)."""
@@ -1232,18 +1214,6 @@ class HipBackend:
             rc = self.lib.dif_wide_coeffs_f64(_ptr(rec), C, int(n_global), _ptr(S), _ptr(V), _ptr(P), DV, _ptr(T), _ptr(partial),
                                               _ptr(B), _ptr(bias), _stream(dev))
         _lib.check(rc, "dif_wide_coeffs_f64")
-        return B, bias
-
-    def wide_scale(self, R, T, partial, C):
-        """R, T float64 [(C+1), DV] -> (B float32 [C, DV], bias float32 [DV]) = (s R[:C], s R[C] + T[C]) -- dif_wide_scale_f64."""
-        dev = _require_device(R, T, partial)
-        DV = R.shape[1]
-        R, T = R.contiguous(), T.contiguous()
-        B = torch.empty((C, DV), dtype=torch.float32, device=dev)
-        bias = torch.empty(DV, dtype=torch.float32, device=dev)
-        with _timed(self, "dif_wide_scale_f64", dev):
-            rc = self.lib.dif_wide_scale_f64(_ptr(R), _ptr(T), _ptr(partial), C, DV, _ptr(B), _ptr(bias), _stream(dev))
-        _lib.check(rc, "dif_wide_scale_f64")
         return B, bias
 
     def layer_tail_mix(self, Z, D, den_col, conv_scale, add, add_scale, rs, bv, x0, prev, alpha, ln_weight, ln_bias, eps,
@@ -1281,7 +1251,7 @@ class HipBackend:
     def simple_layer_wide(self, x, B, bias, D, attn_scale, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias,
                           eps, relu=False):
         """Closed-form `simple` layer for 64 < max(C, D) <= 128 in one pass (csrc/simple_layer_wide.hip): x [n, C], B [C, dv]
-        = [Mn | u | ...], bias [dv] = [cn | cd | ...] (wide_scale), ax = A_hat x [n, C] or None, Wv [D, C] / bv [D] / rs [n]."""
+        = [Mn | u | ...], bias [dv] = [cn | cd | ...] (wide_coeffs), ax = A_hat x [n, C] or None, Wv [D, C] / bv [D] / rs [n]."""
         dev = _require_device(x, B, bias, ax, Wv, bv, rs, x0, ln_weight, ln_bias)
         n, C = x.shape
         for t_, nm in ((x, "x"), (B, "B"), (bias, "bias"), (ax, "ax"), (Wv, "Wv"), (x0, "x0")):

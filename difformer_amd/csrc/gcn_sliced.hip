@@ -45,8 +45,8 @@ using dif::f32x4;
 #define DIF_SLICED_WG_PER_CU 1
 #endif
 // (The timing probes, the 32-bit entry format, the scalar adds, the 8-read sweep and the wall-clock trace that
-// profiles/r04_experiments.md measured live in scripts/variants/gcn_sliced.hip, a fork of this file built by
-// scripts/build_sliced_variants.sh: measurement code does not ship.)  Entries: 16-bit tile-local row numbers in blocks of
+// profiles/r04_experiments.md measured lived in a fork of this file, in the history up to commit 7ecb32a: measurement code
+// does not ship.)  Entries: 16-bit tile-local row numbers in blocks of
 // eight steps x 64 lanes.
 constexpr int kSteps = 8;
 constexpr int kTileRowsMax = DIF_SLICED_TILE_ROWS;   // + 16 zero rows = 10,224 rows x 16 B = 163,584 B of LDS

@@ -29,8 +29,7 @@ constexpr int kWaves = 4;
 #define DIF_HEAD_WAVES 8      // waves per workgroup of the HEAD variant (four 64 x 64 weight blocks in LDS: two workgroups per CU)
 #endif
 constexpr int kHeadWaves = DIF_HEAD_WAVES;
-constexpr int kWStride = 68;     // padded LDS row (floats): 16 lanes x b128 land on 64 distinct banks
-constexpr int kRecordChunksPerCU = 3;   // most workgroups per CU of any kernel that writes partial Gram records
+constexpr int kRecordChunksPerCU = 3;   // partial Gram records per CU that dif_gram_workspace_bytes makes room for
 
 __device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
@@ -408,26 +407,14 @@ int row_chunks(int64_t n_rows, int per_cu, int waves = kWaves) {
     if (p < 1) p = 1;
     return static_cast<int>(p);
 }
-// the Gram kernel: eight waves per workgroup, at least four tiles per wave, one workgroup per CU at most (every
-// workgroup pays a fold and a 16.6-KB partial record)
+// the Gram kernel and the input-layer kernel: eight waves per workgroup, at least four tiles per wave, one workgroup per CU at
+// most (every workgroup pays a fold and a 16.6-KB partial record, the input layer also its weight staging: at the ogbn-proteins
+// rows the input layer takes 36.3 us with one workgroup per CU, 40.6 with two, 50.4 with three; profiles/r06_experiments.md
+// section 8)
 int gram_chunks(int64_t n_rows) {
     const int64_t tiles = (n_rows + 15) / 16;
     int64_t p = (tiles + 4 * kGramWaves - 1) / (4 * kGramWaves);
     if (p > dif::kCUs) p = dif::kCUs;
-    if (p < 1) p = 1;
-    return static_cast<int>(p);
-}
-// the input-layer kernel: ONE workgroup per CU, as the Gram kernel below.  Measured at the ogbn-proteins rows (8,283 tiles = 4.04 per
-// wave, profiles/r06_experiments.md section 8): 36.3 us with one workgroup per CU, 40.6 with two, 50.4 with three -- every workgroup
-// pays its weight staging, the fold of eight waves' Gram accumulators and a 16.6-KB partial record, which costs more than the
-// second round of waves hides.  DIF_INPUT_GRAM_PER_CU=2 / 3 reproduces the comparison.
-int input_gram_chunks(int64_t n_rows) {
-    static const int per_cu = [] { const char* e = getenv("DIF_INPUT_GRAM_PER_CU"); return e ? atoi(e) : 1; }();
-    if (per_cu <= 1) return gram_chunks(n_rows);
-    const int64_t tiles = (n_rows + 15) / 16;
-    int64_t p = (tiles + 2 * kGramWaves - 1) / (2 * kGramWaves);
-    const int64_t cap = static_cast<int64_t>(per_cu > kRecordChunksPerCU ? kRecordChunksPerCU : per_cu) * dif::kCUs;
-    if (p > cap) p = cap;
     if (p < 1) p = 1;
     return static_cast<int>(p);
 }
@@ -705,8 +692,8 @@ struct LayerArgsT {
     const float* ln_w; const float* ln_b; float eps; int relu;
     T* out; int64_t ldo;
     int64_t n_rows; int C, D;
-    // NEXT: the Gram record of `out` (the next layer's input) and its slice-major pre-scaled copy, from the same pass
-    const int32_t* rowptr; f32x4* ys_next; int64_t npad; float* ws; int64_t ws_stride;
+    // the slice-major pre-scaled copy of `out` (the next layer's SpMM operand), from the same pass
+    const int32_t* rowptr; f32x4* ys_next; int64_t npad;
     // HEAD: the model's output Linear (difformer.py:208) applied to the finished rows in the same pass
     const float* Wo; const float* bo; int Co; T* logits; int64_t ldl;
     // GATHER: the aggregation itself in this pass (sparse graphs: a few entries per row) -- CSR over destination rows
@@ -811,7 +798,7 @@ __device__ __forceinline__ bf16x8 cat8(const bf16x4& a, const bf16x4& b) {
 // l15 exactly once -> no bank conflicts.  (The row-major layout with a 68-float stride, conflict-free for groups of 16
 // CONSECUTIVE lanes, put lanes (0, 12) and (1, 11) of the first hardware group on one quad: SQ_LDS_BANK_CONFLICT was 34 %
 // of the kernel's LDS cycles, profiles/r02_pmc_traffic_c4.json.)
-constexpr int kWBlock = 64 * 64;           // (the NEXT variant folds 2 x 40 x 64 floats through the two blocks: 8,192 there)
+constexpr int kWBlock = 64 * 64;
 __device__ __forceinline__ int widx(int f, int c) {
     return ((((f >> 4) * 4 + (c >> 4)) * 4 + ((c >> 2) & 3)) << 6) + ((f & 15) << 2) + (c & 3);
 }
@@ -860,13 +847,13 @@ __device__ __forceinline__ void project_split(f32x4 (&y)[4], const f32x4 (&xa)[4
 }
 
 #ifndef DIF_GATHER_WG
-#define DIF_GATHER_WG 4           // workgroups per CU the GATHER variants are compiled for (probes / old layouts: scripts/variants/simple_layer.hip)
+#define DIF_GATHER_WG 4           // workgroups per CU the GATHER variants are compiled for
 #endif
-template <bool EXACT, bool GRAPH_W, bool NEXT, typename T = float, bool HEAD = false, bool GATHER = false, bool SPLIT = false>
+template <bool EXACT, bool GRAPH_W, typename T = float, bool HEAD = false, bool GATHER = false, bool SPLIT = false>
 __global__ __launch_bounds__(64 * (HEAD ? kHeadWaves : kWaves),
-                             HEAD ? (2 * kHeadWaves + 3) / 4 : (NEXT ? 2 : (GATHER ? DIF_GATHER_WG : 4)))
+                             HEAD ? (2 * kHeadWaves + 3) / 4 : (GATHER ? DIF_GATHER_WG : 4))
 void simple_layer_kernel(LayerArgsT<T> a) {
-    static_assert(!SPLIT || (EXACT && !NEXT), "split-bf16 products: the dense 64 x 64 float32 layers");
+    static_assert(!SPLIT || EXACT, "split-bf16 products: the dense 64 x 64 float32 layers");
     constexpr int NW = HEAD ? kHeadWaves : kWaves;          // waves per workgroup
     __shared__ __attribute__((aligned(16))) float sm_w[2][kWBlock];   // MnT, Wv (zero padded; widx layout)
     // HEAD: up to 128 output classes as split-bf16 A fragments, [hi | lo][(blk * 4 + ft) * 2 + kb][lane]: lane (lg, l15) holds
@@ -874,8 +861,6 @@ void simple_layer_kernel(LayerArgsT<T> a) {
     __shared__ __attribute__((aligned(16))) bf16x8 sm_wo[HEAD ? 2 : 1][HEAD ? 16 * 64 : 1];
     __shared__ __attribute__((aligned(16))) float sm_bo[HEAD ? 128 : 4];
     __shared__ __attribute__((aligned(16))) float sm_cn[64], sm_u[64], sm_bv[64], sm_lw[64], sm_lb[64];
-    __shared__ __attribute__((aligned(16))) float sm_t[NEXT ? NW : 1][16 * kWStride];   // NEXT: a wave's finished tile
-    __shared__ float sm_s[NW][64];
     __shared__ float sm_cd;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, lg = lane >> 4;
@@ -960,11 +945,6 @@ void simple_layer_kernel(LayerArgsT<T> a) {
     __syncthreads();
     const float cd = sm_cd;
     const float inv_d = 1.0f / static_cast<float>(D);
-
-    f32x4 gacc[NEXT ? 10 : 1];          // NEXT: upper half of out^T out (see gram_kernel)
-    f32x4 gsx = zero4();
-#pragma unroll
-    for (int i = 0; i < (NEXT ? 10 : 1); ++i) gacc[i] = zero4();
 
     auto body = [&](int64_t tile, auto guard_tag) {
         constexpr bool G = decltype(guard_tag)::value;
@@ -1055,7 +1035,7 @@ void simple_layer_kernel(LayerArgsT<T> a) {
                         *reinterpret_cast<const f32x4*>(&sm_lb[16 * ft + 4 * lg]);
         }
         float dscale = 0.f;
-        if (!NEXT && a.ys_next && row_ok) dscale = dinv_of(a.rowptr, row);
+        if (a.ys_next && row_ok) dscale = dinv_of(a.rowptr, row);
         if constexpr (HEAD) {
             // logits^T = Wo out^T: the finished row piece has the layout of a loaded x fragment (features 16ft + 4lg .. + 3
             // of row r0 + l15), so it is the B operand of the same transposed product; two blocks of 64 classes
@@ -1117,33 +1097,10 @@ void simple_layer_kernel(LayerArgsT<T> a) {
                 else
                     for (int r = 0; r < 4; ++r) if (f + r < D) Elem<T>::st(a.out + row * a.ldo + f + r, v[r]);
             }
-            if (!NEXT && a.ys_next) {
+            if (a.ys_next) {
                 // slice-major pre-scaled copy for the next layer's SpMM straight from the registers: this lane holds
                 // slice 4ft + lg of its row, the 16 lanes of a group 16 consecutive rows -> 256 contiguous bytes
                 if (row_ok && (EXACT || f < D)) a.ys_next[static_cast<int64_t>(4 * ft + lg) * a.npad + row] = v * dscale;
-            }
-            if (NEXT) {         // park the finished row piece (zero outside the matrix) for the row-contracting re-read
-                if (!(row_ok && (EXACT || f < D))) v = zero4();
-                else if (!EXACT)
-                    for (int r = 0; r < 4; ++r) if (f + r >= D) v[r] = 0.f;
-                *reinterpret_cast<f32x4*>(&sm_t[wave][l15 * kWStride + f]) = v;
-            }
-        }
-        if (NEXT) {
-            // the tile again, four whole rows per read (row 4u + lg, columns 4*l15..+3): operand of the Gram product
-            // contracting over rows, and one 16-byte slice of the row for the slice-major copy
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const f32x4 xv = *reinterpret_cast<const f32x4*>(&sm_t[wave][(4 * u + lg) * kWStride + 4 * l15]);
-                const int64_t r2 = tile * 16 + 4 * u + lg;
-                if (a.ys_next && (!G || r2 < a.n_rows) && 4 * l15 < D) a.ys_next[static_cast<int64_t>(l15) * a.npad + r2] = xv * dinv_of(a.rowptr, r2);
-                gsx += xv;
-                int i = 0;
-#pragma unroll
-                for (int ta = 0; ta < 4; ++ta)
-#pragma unroll
-                    for (int tb = ta; tb < 4; ++tb, ++i)
-                        gacc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[ta], xv[tb], gacc[i], 0, 0, 0);
             }
         }
     };
@@ -1158,69 +1115,12 @@ void simple_layer_kernel(LayerArgsT<T> a) {
         asm volatile("" ::: "memory");
         body(tile, std::true_type{});
     }
-    if (!NEXT && a.ys_next) {
+    if (a.ys_next) {
         const int64_t pad = a.npad - a.n_rows;          // rows of the copy past the matrix are read by the last source tile
         for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < pad * 16;
              i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
             const int64_t sl = i / pad, r = a.n_rows + i % pad;
             if (4 * sl < D) a.ys_next[sl * a.npad + r] = zero4();
-        }
-    }
-    if (NEXT) {
-        const int64_t pad = a.ys_next ? a.npad - a.n_rows : 0;   // rows of the copy past the matrix are read by the last source tile
-        for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < pad * 16;
-             i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-            const int64_t sl = i / pad, r = a.n_rows + i % pad;
-            if (4 * sl < D) a.ys_next[sl * a.npad + r] = zero4();
-        }
-        // fold the four waves' Gram partials through the weight region (no longer needed): (w0 + w2) + (w1 + w3)
-        __syncthreads();
-        float* buf = &sm_w[0][0];                       // 2 x 40 x 64 floats needed, 2 x 64 x 68 there (NEXT keeps the padded size)
-        if (wave >= 2) {
-#pragma unroll
-            for (int i = 0; i < 10; ++i)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) buf[((wave - 2) * 40 + i * 4 + reg) * 64 + lane] = gacc[i][reg];
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            float v = gsx[t];
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            if (lg == 0) sm_s[wave][4 * l15 + t] = v;
-        }
-        __syncthreads();
-        if (wave < 2) {
-#pragma unroll
-            for (int i = 0; i < 10; ++i)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) gacc[i][reg] += buf[(wave * 40 + i * 4 + reg) * 64 + lane];
-        }
-        __syncthreads();
-        if (wave == 1) {
-#pragma unroll
-            for (int i = 0; i < 10; ++i)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) buf[(i * 4 + reg) * 64 + lane] = gacc[i][reg];
-        }
-        __syncthreads();
-        if (wave == 0) {
-            float* rec = a.ws + static_cast<int64_t>(blockIdx.x) * a.ws_stride;
-            int i = 0;
-#pragma unroll
-            for (int ta = 0; ta < 4; ++ta)
-#pragma unroll
-                for (int tb = ta; tb < 4; ++tb, ++i)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) {
-                        const float v = gacc[i][reg] + buf[(i * 4 + reg) * 64 + lane];
-                        const int gi = 4 * (4 * lg + reg) + ta, gj = 4 * l15 + tb;
-                        if (gi < D && gj < D) {
-                            rec[gi * D + gj] = v;
-                            if (ta != tb) rec[gj * D + gi] = v;
-                        }
-                    }
-            if (lane < D) rec[D * D + lane] = ((sm_s[0][lane] + sm_s[1][lane]) + sm_s[2][lane]) + sm_s[3][lane];
         }
     }
 }
@@ -1290,7 +1190,7 @@ extern "C" int dif_input_gram_f32(const float* x, int64_t ldx, int64_t n_rows, i
         DIF_REQUIRE(plan[0] == D / 4 && npad >= n_rows, DIF_E_BADARG, "dif_input_gram: plan does not match D / n_rows");
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int P = input_gram_chunks(n_rows);
+    const int P = gram_chunks(n_rows);
     const int64_t rec = (static_cast<int64_t>(D) * D + D + 3) & ~int64_t(3);
     float* ws = static_cast<float*>(workspace);
     const int xvec = (C_in % 4 == 0) && (ldx % 4 == 0) && dif::aligned16(x);
@@ -1558,13 +1458,13 @@ template <typename T>
 int layer_entry(const T* x, int64_t ldx, int64_t n_rows, int C, int D, const float* coef, const T* ax, int64_t ldax,
                 const float* Wv, const float* bv, const float* row_sums, float gcn_scale, const T* x0, int64_t ldx0,
                 int residual, float alpha, const float* ln_weight, const float* ln_bias, float ln_eps, int relu, T* out,
-                int64_t ldo, float* next_record, const int32_t* rowptr, const int32_t* plan, float* next_ys, void* workspace,
-                size_t workspace_bytes, dif_stream_t stream, const float* Wo = nullptr, const float* bo = nullptr, int Co = 0,
+                int64_t ldo, const int32_t* rowptr, const int32_t* plan, float* next_ys, dif_stream_t stream,
+                const float* Wo = nullptr, const float* bo = nullptr, int Co = 0,
                 T* logits = nullptr, int64_t ldl = 0, const int32_t* g_rowptr = nullptr, const int32_t* g_src = nullptr,
                 const float* g_val = nullptr) {
     const bool head = Wo != nullptr;
     DIF_REQUIRE(x && coef && (out || head) && n_rows > 0, DIF_E_BADARG, "dif_simple_layer: null pointer or no rows");
-    DIF_REQUIRE(!head || (bo && logits && Co > 0 && Co <= 128 && ldl >= Co && !next_record && !next_ys), DIF_E_BADARG,
+    DIF_REQUIRE(!head || (bo && logits && Co > 0 && Co <= 128 && ldl >= Co && !next_ys), DIF_E_BADARG,
                 "dif_simple_layer: the fused output Linear needs bo, logits, 1 <= Co <= 128, ldl >= Co, no next-layer products");
     DIF_REQUIRE(C > 0 && C <= 64 && C % 4 == 0 && D > 0 && D <= 64, DIF_E_SHAPE,
                 "dif_simple_layer: covers C <= 64 (C %% 4 == 0) and D <= 64 (got %d, %d)", C, D);
@@ -1580,62 +1480,52 @@ int layer_entry(const T* x, int64_t ldx, int64_t n_rows, int C, int D, const flo
     DIF_REQUIRE(!residual || C == D, DIF_E_SHAPE, "dif_simple_layer: the residual needs C == D");
     DIF_REQUIRE(!x0 || ldx0 >= D, DIF_E_BADARG, "dif_simple_layer: ldx0 smaller than a row");
     const bool f32 = std::is_same<T, float>::value;
-    DIF_REQUIRE(f32 || (!next_record && !next_ys), DIF_E_BADARG, "dif_simple_layer: products for the next layer are float32-only");
-    const bool next = next_record != nullptr;          // Gram record of the output from the same pass (slower)
+    DIF_REQUIRE(f32 || !next_ys, DIF_E_BADARG, "dif_simple_layer: products for the next layer are float32-only");
     const bool gather = g_rowptr != nullptr;
-    const int P = head ? row_chunks(n_rows, 2, kHeadWaves) : row_chunks(n_rows, next ? kRecordChunksPerCU : (gather ? DIF_GATHER_WG : 4));
-    const int64_t rec = (static_cast<int64_t>(D) * D + D + 3) & ~int64_t(3);
+    const int P = head ? row_chunks(n_rows, 2, kHeadWaves) : row_chunks(n_rows, gather ? DIF_GATHER_WG : 4);
     int64_t npad = 0;
-    if (next) {
-        DIF_REQUIRE(workspace && workspace_bytes >= dif_gram_workspace_bytes(n_rows, D), DIF_E_WORKSPACE,
-                    "dif_simple_layer: workspace too small for the next record (dif_gram_workspace_bytes(n_rows, D))");
-    }
-    if (next || next_ys) {
+    if (next_ys) {
         DIF_REQUIRE(D % 4 == 0, DIF_E_SHAPE, "dif_simple_layer: products for the next layer need D %% 4 == 0");
-        DIF_REQUIRE((next_ys == nullptr) || (rowptr && plan && dif::aligned16(next_ys)), DIF_E_BADARG,
+        DIF_REQUIRE(rowptr && plan && dif::aligned16(next_ys), DIF_E_BADARG,
                     "dif_simple_layer: the slice-major copy needs rowptr, the plan and a 16-byte aligned buffer");
-        if (next_ys) {
-            npad = static_cast<int64_t>(plan[6]) * plan[7];
-            DIF_REQUIRE(plan[0] == D / 4 && npad >= n_rows, DIF_E_BADARG, "dif_simple_layer: plan does not match D / n_rows");
-        }
+        npad = static_cast<int64_t>(plan[6]) * plan[7];
+        DIF_REQUIRE(plan[0] == D / 4 && npad >= n_rows, DIF_E_BADARG, "dif_simple_layer: plan does not match D / n_rows");
     }
-    DIF_REQUIRE(!gather || (g_src && g_val && !ax && !next && !next_ys), DIF_E_BADARG,
+    DIF_REQUIRE(!gather || (g_src && g_val && !ax && !next_ys), DIF_E_BADARG,
                 "dif_simple_layer: the in-kernel aggregation takes rowptr, src AND val, no ax and no next-layer products");
     LayerArgsT<T> a = {x, ldx, ax, ldax, coef, Wv, bv, row_sums, gcn_scale, x0, ldx0, residual, alpha, ln_weight, ln_bias, ln_eps,
-                       relu, out, ldo, n_rows, C, D, rowptr, reinterpret_cast<f32x4*>(next_ys), npad, static_cast<float*>(workspace), rec,
-                       Wo, bo, Co, logits, ldl, g_rowptr, g_src, g_val};
+                       relu, out, ldo, n_rows, C, D, rowptr, reinterpret_cast<f32x4*>(next_ys), npad, Wo, bo, Co, logits, ldl,
+                       g_rowptr, g_src, g_val};
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool exact = C == 64 && D == 64 && ldo % 4 == 0 && (!x0 || ldx0 % 4 == 0);
     const bool gw = (ax != nullptr || gather) && Wv != nullptr;
     // dense 64 x 64 float32 layers (the headline shape): both products on split-bfloat16 operands unless DIFFORMER_EXACT_FP32=1
-    const bool split = exact && f32 && !next && !gather && !dif::exact_fp32() &&
+    const bool split = exact && f32 && !gather && !dif::exact_fp32() &&
                        (reinterpret_cast<uintptr_t>(coef) & 15u) == 0 && (!gw || (reinterpret_cast<uintptr_t>(Wv) & 15u) == 0);
     if (split) {
         if constexpr (std::is_same<T, float>::value) {
             if (head) {
-                if (gw) hipLaunchKernelGGL((simple_layer_kernel<true, true, false, T, true, false, true>), dim3(P), dim3(64 * kHeadWaves), 0, st, a);
-                else hipLaunchKernelGGL((simple_layer_kernel<true, false, false, T, true, false, true>), dim3(P), dim3(64 * kHeadWaves), 0, st, a);
+                if (gw) hipLaunchKernelGGL((simple_layer_kernel<true, true, T, true, false, true>), dim3(P), dim3(64 * kHeadWaves), 0, st, a);
+                else hipLaunchKernelGGL((simple_layer_kernel<true, false, T, true, false, true>), dim3(P), dim3(64 * kHeadWaves), 0, st, a);
             } else {
-                if (gw) hipLaunchKernelGGL((simple_layer_kernel<true, true, false, T, false, false, true>), dim3(P), dim3(64 * kWaves), 0, st, a);
-                else hipLaunchKernelGGL((simple_layer_kernel<true, false, false, T, false, false, true>), dim3(P), dim3(64 * kWaves), 0, st, a);
+                if (gw) hipLaunchKernelGGL((simple_layer_kernel<true, true, T, false, false, true>), dim3(P), dim3(64 * kWaves), 0, st, a);
+                else hipLaunchKernelGGL((simple_layer_kernel<true, false, T, false, false, true>), dim3(P), dim3(64 * kWaves), 0, st, a);
             }
             return dif::launch_status("simple_layer_kernel");
         }
     }
-#define DIF_LAYER(E, G, N) hipLaunchKernelGGL((simple_layer_kernel<E, G, N, T>), dim3(P), dim3(64 * kWaves), 0, st, a)
-#define DIF_LAYER_HEAD(E, G) hipLaunchKernelGGL((simple_layer_kernel<E, G, false, T, true>), dim3(P), dim3(64 * kHeadWaves), 0, st, a)
-#define DIF_LAYER_GATHER(E, G, H) hipLaunchKernelGGL((simple_layer_kernel<E, G, false, T, H, true>), dim3(P), dim3(64 * (H ? kHeadWaves : kWaves)), 0, st, a)
+#define DIF_LAYER(E, G) hipLaunchKernelGGL((simple_layer_kernel<E, G, T>), dim3(P), dim3(64 * kWaves), 0, st, a)
+#define DIF_LAYER_HEAD(E, G) hipLaunchKernelGGL((simple_layer_kernel<E, G, T, true>), dim3(P), dim3(64 * kHeadWaves), 0, st, a)
+#define DIF_LAYER_GATHER(E, G, H) hipLaunchKernelGGL((simple_layer_kernel<E, G, T, H, true>), dim3(P), dim3(64 * (H ? kHeadWaves : kWaves)), 0, st, a)
 #define DIF_LAYER2(E, G) do { if (gather) { if (head) DIF_LAYER_GATHER(E, G, true); else DIF_LAYER_GATHER(E, G, false); } \
-                              else if (head) DIF_LAYER_HEAD(E, G); else if (f32 && next) DIF_LAYER(E, G, (std::is_same<T, float>::value)); else DIF_LAYER(E, G, false); } while (0)
+                              else if (head) DIF_LAYER_HEAD(E, G); else DIF_LAYER(E, G); } while (0)
     if (exact) { if (gw) DIF_LAYER2(true, true); else DIF_LAYER2(true, false); }
     else { if (gw) DIF_LAYER2(false, true); else DIF_LAYER2(false, false); }
 #undef DIF_LAYER2
 #undef DIF_LAYER_GATHER
 #undef DIF_LAYER_HEAD
 #undef DIF_LAYER
-    if (int rc = dif::launch_status("simple_layer_kernel")) return rc;
-    if (next) return dif::launch_record_finalize(static_cast<float*>(workspace), P, rec, D * D + D, 0, next_record, st);
-    return 0;
+    return dif::launch_status("simple_layer_kernel");
 }
 }  // namespace
 
@@ -1643,11 +1533,10 @@ extern "C" int dif_simple_layer_f32(const float* x, int64_t ldx, int64_t n_rows,
                                     const float* ax, int64_t ldax, const float* Wv, const float* bv, const float* row_sums,
                                     float gcn_scale, const float* x0, int64_t ldx0, int residual, float alpha,
                                     const float* ln_weight, const float* ln_bias, float ln_eps, int relu, float* out,
-                                    int64_t ldo, float* next_record, const int32_t* rowptr, const int32_t* plan,
-                                    float* next_ys, void* workspace, size_t workspace_bytes, dif_stream_t stream) {
+                                    int64_t ldo, const int32_t* rowptr, const int32_t* plan, float* next_ys,
+                                    dif_stream_t stream) {
     return layer_entry<float>(x, ldx, n_rows, C, D, coef, ax, ldax, Wv, bv, row_sums, gcn_scale, x0, ldx0, residual, alpha,
-                              ln_weight, ln_bias, ln_eps, relu, out, ldo, next_record, rowptr, plan, next_ys, workspace,
-                              workspace_bytes, stream);
+                              ln_weight, ln_bias, ln_eps, relu, out, ldo, rowptr, plan, next_ys, stream);
 }
 
 // The LAST layer of a model with the output Linear of difformer.py:208 in the same pass: logits [n, Co] = out Wo^T + bo
@@ -1660,7 +1549,7 @@ extern "C" int dif_simple_layer_head_f32(const float* x, int64_t ldx, int64_t n_
                                          int64_t ldl, dif_stream_t stream) {
     DIF_REQUIRE(Wo != nullptr, DIF_E_BADARG, "dif_simple_layer_head_f32: Wo is null");
     return layer_entry<float>(x, ldx, n_rows, C, D, coef, ax, ldax, Wv, bv, row_sums, gcn_scale, x0, ldx0, residual, alpha,
-                              ln_weight, ln_bias, ln_eps, relu, out, ldo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream,
+                              ln_weight, ln_bias, ln_eps, relu, out, ldo, nullptr, nullptr, nullptr, stream,
                               Wo, bo, Co, logits, ldl);
 }
 
@@ -1675,7 +1564,7 @@ extern "C" int dif_simple_layer_gather_f32(const float* x, int64_t ldx, int64_t 
                                            int64_t ldl, dif_stream_t stream) {
     DIF_REQUIRE(rowptr && src && val, DIF_E_BADARG, "dif_simple_layer_gather_f32: rowptr / src / val are null");
     return layer_entry<float>(x, ldx, n_rows, C, D, coef, nullptr, 0, Wv, bv, nullptr, gcn_scale, x0, ldx0, residual, alpha,
-                              ln_weight, ln_bias, ln_eps, relu, out, ldo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream,
+                              ln_weight, ln_bias, ln_eps, relu, out, ldo, nullptr, nullptr, nullptr, stream,
                               Wo, bo, Co, logits, ldl, rowptr, src, val);
 }
 
@@ -1689,7 +1578,7 @@ extern "C" int dif_simple_layer_gather_bf16(const void* x, int64_t ldx, int64_t 
     DIF_REQUIRE(rowptr && src && val, DIF_E_BADARG, "dif_simple_layer_gather_bf16: rowptr / src / val are null");
     return layer_entry<B>(static_cast<const B*>(x), ldx, n_rows, C, D, coef, nullptr, 0, Wv, bv, nullptr, gcn_scale,
                           static_cast<const B*>(x0), ldx0, residual, alpha, ln_weight, ln_bias, ln_eps, relu, static_cast<B*>(out),
-                          ldo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream, Wo, bo, Co, static_cast<B*>(logits), ldl,
+                          ldo, nullptr, nullptr, nullptr, stream, Wo, bo, Co, static_cast<B*>(logits), ldl,
                           rowptr, src, val);
 }
 
@@ -1704,7 +1593,7 @@ extern "C" int dif_simple_layer_head_bf16(const void* x, int64_t ldx, int64_t n_
     DIF_REQUIRE(Wo != nullptr, DIF_E_BADARG, "dif_simple_layer_head_bf16: Wo is null");
     return layer_entry<B>(static_cast<const B*>(x), ldx, n_rows, C, D, coef, static_cast<const B*>(ax), ldax, Wv, bv, row_sums,
                           gcn_scale, static_cast<const B*>(x0), ldx0, residual, alpha, ln_weight, ln_bias, ln_eps, relu,
-                          static_cast<B*>(out), ldo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream, Wo, bo, Co,
+                          static_cast<B*>(out), ldo, nullptr, nullptr, nullptr, stream, Wo, bo, Co,
                           static_cast<B*>(logits), ldl);
 }
 
@@ -1717,5 +1606,5 @@ extern "C" int dif_simple_layer_bf16(const void* x, int64_t ldx, int64_t n_rows,
     using B = dif::bf16;
     return layer_entry<B>(static_cast<const B*>(x), ldx, n_rows, C, D, coef, static_cast<const B*>(ax), ldax, Wv, bv, row_sums,
                           gcn_scale, static_cast<const B*>(x0), ldx0, residual, alpha, ln_weight, ln_bias, ln_eps, relu,
-                          static_cast<B*>(out), ldo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream);
+                          static_cast<B*>(out), ldo, nullptr, nullptr, nullptr, stream);
 }

@@ -374,7 +374,7 @@ extern "C" int dif_gram128_f32(const float* x, int64_t ldx, int64_t n_rows, int 
 }
 
 // Closed-form `simple` layer for 64 < max(C, D) <= 128 (C % 4 == 0, D % 4 == 0) in one pass; see the head of this file.
-//   bmat [C][dv] (dv >= D + 1; the host's dif_wide_scale_f64 output: columns [0, D) = s Mn, column D = s u), bias [dv] = cn | cd;
+//   bmat [C][dv] (dv >= D + 1; dif_wide_coeffs_f64's output: columns [0, D) = s Mn, column D = s u), bias [dv] = cn | cd;
 //   ax (nullable) = A_hat x unscaled [n, C]; Wv [D][C], bv [D], rs [n] (nullable together: use_weight = False needs C == D);
 //   x0 (nullable) [n, D]; residual mixes with x itself (needs C == D).
 extern "C" int dif_simple_layer_wide_f32(const float* x, int64_t ldx, int64_t n_rows, int C, int D, const float* bmat, int dv,

@@ -34,7 +34,7 @@ __device__ __forceinline__ bf16x8 cat8(const bf16x4& a, const bf16x4& b) {
 }
 
 constexpr int kXWaves = 8;             // 128 rows per workgroup and weight chunk
-// (timing probes: scripts/variants/simple_layer_xwide.hip, built by scripts/build_sliced_variants.sh)
+// (timing probes: a fork of this file, in the history up to commit 7ecb32a)
 
 struct XArgs {
     const float* x; int64_t ldx;
@@ -313,7 +313,7 @@ extern "C" int64_t dif_xwide_packed_bytes(int C, int D) {
     return static_cast<int64_t>(g.fc) * 2 * g.kb * 128 * 16;
 }
 
-// src: [C][ld] with the matrix in columns [0, D) when transposed (the [Mn | u] operand of dif_wide_scale_f64), else [D][ld]
+// src: [C][ld] with the matrix in columns [0, D) when transposed (the [Mn | u] operand of dif_wide_coeffs_f64), else [D][ld]
 // (an nn.Linear weight [D, C]).  packed: dif_xwide_packed_bytes(C, D), 16-byte aligned.
 extern "C" int dif_xwide_pack_f32(const float* src, int64_t ld, int transposed, int C, int D, void* packed, dif_stream_t stream) {
     DIF_REQUIRE(src && packed && xwide_covers(C, D) && dif::aligned16(packed), DIF_E_BADARG,

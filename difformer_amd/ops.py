@@ -807,8 +807,8 @@ def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_sca
     (instead of the KtV record) and ONE all-gather of the source rows (x instead of v), started first so that the
     Gram pass and the coefficients run under it.
     `carry` (dict, optional; single GPU) chains layers over the same graph: with carry["want_next"] the layer kernel also
-    writes the slice-major pre-scaled copy of its output (the next layer's SpMM operand) from its registers, and with
-    carry["next_record"] the Gram record of the output too; the next layer picks up what it finds.
+    writes the slice-major pre-scaled copy of its output (the next layer's SpMM operand) from its registers; the next layer
+    picks it up.
     `keep` (dict, optional; the training forward, autograd_ops._ClosedFormLayer): receives the record, the coefficients, the
     aggregated rows and the row sums the backward pass starts from (the aggregation then stays a launch of its own)."""
     be = get_backend()
@@ -859,8 +859,7 @@ def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_sca
     ax = rs = gather = None
     want_next = (carry is not None and not sharded and carry.get("want_next", False) and D % 4 == 0 and D == C and
                  x.dtype == torch.float32)
-    want_rec = want_next and carry.get("next_record", False)
-    if (csr is not None and sl is None and not sharded and not want_rec and keep is None and LAYER_GATHER and csr.n_blocks == 1 and n == csr.num_nodes and
+    if (csr is not None and sl is None and not sharded and keep is None and LAYER_GATHER and csr.n_blocks == 1 and n == csr.num_nodes and
             0 < csr.nnz <= LAYER_GATHER_MAX_DEGREE * n and hasattr(be, "_simple_layer_gather") and
             csr.max_degree() <= LAYER_GATHER_MAX_ROW):
         # a few entries per row: the layer kernel walks the CSR itself, no separate SpMM launch and no `ax` round trip
@@ -895,12 +894,11 @@ def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_sca
     if gather is not None:
         return be.simple_layer(x, coef, D, None, Wv, bv, None, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
                                gather=gather)
-    if not (want_next and (sl is not None or want_rec)):
+    if not (want_next and sl is not None):
         return be.simple_layer(x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu)
-    out, ys2, record2 = be.simple_layer(x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps,
-                                        relu, csr.rowptr if sl is not None else None, sl.plan if sl is not None else None,
-                                        want_rec)
-    carry["products"] = dict(x=out, sl=sl, record=record2, ys=ys2)
+    out, ys2 = be.simple_layer(x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
+                               csr.rowptr, sl.plan)
+    carry["products"] = dict(x=out, sl=sl, record=None, ys=ys2)
     return out
 
 
@@ -1010,15 +1008,12 @@ class WideCoefficients:
         self.V = V
 
 
-WIDE_COEFFS_OWN = os.environ.get("DIFFORMER_WIDE_COEFFS_LIBRARY", "0") != "1"      # 1: the two float64 library GEMMs of round 4
-
-
 def simple_layer_closed_form_wide(x, coeffs: WideCoefficients, Wv, bv, csr, attn_scale, gcn_scale, x0, residual, alpha,
                                   ln_weight, ln_bias, eps):
     """The closed form of simple_layer_closed_form at the widths the reference's scripts train with (hidden 128 / 300 /
     400: run.sh): query == source == x [n, C] fp32, one head, single GPU, inference.
         G~ = [X | 1]^T [X | 1]             one streaming pass (dif_gram_sym_f32: the upper 64-blocks of X^T X on the fp32 MFMA)
-        [Mn | u], [cn | cd]                two float64 library GEMMs on (C + 1)-square matrices (WideCoefficients)
+        [Mn | u], [cn | cd]                the float64 (C + 1)-square products of WideCoefficients (dif_wide_coeffs_f64)
         Z = x [Mn | u] + [cn | cd]         ONE row GEMM: numerator | denominator
         gcn = (A_hat x) Wv^T               SpMM on x, one row GEMM  (+ (A_hat 1) bv^T inside the tail)
         tail                               num / den, combine, + x0, residual, LayerNorm in one pass (dif_layer_tail_mix_f32)
@@ -1029,13 +1024,7 @@ def simple_layer_closed_form_wide(x, coeffs: WideCoefficients, Wv, bv, csr, attn
     D = coeffs.D
     x3 = x.reshape(n, 1, C)
     rec = be.gram_sym(x)                                                # [X^T X (upper blocks) | sum x | ...]
-    if hasattr(be, "wide_coeffs") and WIDE_COEFFS_OWN:
-        B, bias = be.wide_coeffs(rec, C, n, coeffs.S, coeffs.V, coeffs.P)   # both float64 products + bookkeeping: two launches
-    else:
-        Gt, partial = be.wide_gram(rec, C, n, coeffs.S)                 # G~ (float64) and the partial sums of |Q|^2, |K|^2
-        T = Gt @ coeffs.V                                               # [(C+1), D+4]
-        R = coeffs.P @ T
-        B, bias = be.wide_scale(R, T, partial, C)                       # [Mn | u | 0 0 0], [cn | cd | 0 0 0] (float32)
+    B, bias = be.wide_coeffs(rec, C, n, coeffs.S, coeffs.V, coeffs.P)   # both float64 products + bookkeeping: two launches
     if max(C, D) <= 128 and not EXACT_FP32 and hasattr(be, "simple_layer_wide"):
         # hidden 128 (node classification/run.sh:42-44): both row products, the division, the combine, the residual and the
         # LayerNorm in ONE pass over the rows (csrc/simple_layer_wide.hip) -- no library GEMM, no [n, D + 4] intermediate

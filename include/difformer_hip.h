@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define DIF_ABI_VERSION 2   /* 2: dif_csr_build's status is int32[2] (status[1] = longest row): a caller that allocates one int must be rebuilt */
+#define DIF_ABI_VERSION 3   /* 2: dif_csr_build's status is int32[2] (status[1] = longest row): a caller that allocates one int must be rebuilt
+                               3: dif_simple_layer_f32 no longer writes the next layer's Gram record (its record and
+                                  workspace parameters are gone); dif_wide_coeffs_f64 is the only wide-coefficient entry point */
 
 #define DIF_E_BADARG   (-1)  /* null pointer, non-positive size, misaligned pointer */
 #define DIF_E_SHAPE    (-2)  /* shape the kernels do not cover */
@@ -256,8 +258,6 @@ int dif_row_order(const int32_t* rowptr, int64_t row_begin, int64_t n_rows, int3
  *                          (NULL when bv is not needed); residual = 0 skips the alpha mix, ln_weight = NULL the LayerNorm.
  *                          next_ys != NULL: the pass also writes the slice-major copy of `out` scaled by deg^-1/2 (what
  *                          dif_gram_f32 would write for the next layer), 256 contiguous bytes per lane group.
- *                          next_record != NULL: it leaves dif_gram_f32's record of `out` as well (workspace >=
- *                          dif_gram_workspace_bytes(n_rows, D)); measured slower than a separate dif_gram_f32 at C4.
  * ------------------------------------------------------------------------------------- */
 size_t dif_gram_workspace_bytes(int64_t n_rows, int C);
 int dif_gram_f32(const float* x, int64_t ldx, int64_t n_rows, int C, const int32_t* rowptr, const int32_t* plan,
@@ -278,8 +278,7 @@ int dif_simple_layer_f32(const float* x, int64_t ldx, int64_t n_rows, int C, int
                          const float* ax, int64_t ldax, const float* Wv, const float* bv, const float* row_sums,
                          float gcn_scale, const float* x0, int64_t ldx0, int residual, float alpha,
                          const float* ln_weight, const float* ln_bias, float ln_eps, int relu, float* out,
-                         int64_t ldo, float* next_record, const int32_t* rowptr, const int32_t* plan, float* next_ys,
-                         void* workspace, size_t workspace_bytes, dif_stream_t stream);
+                         int64_t ldo, const int32_t* rowptr, const int32_t* plan, float* next_ys, dif_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * a3, dense graphs without edge weights: feature-sliced product with the source rows staged in LDS
@@ -479,22 +478,12 @@ int dif_simple_coeffs_bg_f32(const float* gt, const float* pt, const float* vtt,
 size_t dif_gram_sym_workspace_bytes(int64_t n_rows, int C);
 int dif_gram_sym_f32(const float* x, int64_t ldx, int64_t n_rows, int C, float* record, void* workspace,
                      size_t workspace_bytes, dif_stream_t stream);
-/* Float64 bookkeeping of that closed form around its two library GEMMs (csrc/wide_coeffs.hip):
- *   dif_wide_gram_f64   Gt double[(C+1)^2] = [[X^T X, sx], [sx^T, n_global]] from the record of dif_gram_sym_f32 (lower
- *                       blocks mirrored), and partial double[2 * dif_wide_partials(C)]: per-workgroup sums of
- *                       <S[0], Gt> = |Q|^2 and <S[1], Gt> = |K|^2 with S double[2][(C+1)^2] = {W~q^T W~q, W~k^T W~k}
- *   dif_wide_scale_f64  s = 1 / (|Q| |K|) from the partial sums; B float[C][DV] = s R[0..C), bias float[DV] = s R[C] + T[C]
- *                       for R, T double[(C+1)][DV] (R = P~ T, T = Gt V~): the operands of the row GEMM x B + bias. */
-int64_t dif_wide_partials(int C);
-int dif_wide_gram_f64(const float* record, int C, int64_t n_global, const double* S, double* Gt, double* partial,
-                      dif_stream_t stream);
-int dif_wide_scale_f64(const double* R, const double* T, const double* partial, int C, int DV, float* B, float* bias,
-                       dif_stream_t stream);
-/* Round 5: the same coefficients WITHOUT the two library GEMMs -- record (dif_gram_sym_f32 / dif_gram128_f32) -> B float [C][DV] =
-   s R[0..C) and bias float [DV] = s R[C] + T[C] in two launches (T = G~ V~ straight from the record with the partial norm
-   products; R = P~ T with the scaling).  S double [2][(C+1)^2], V double [(C+1)][DV], P double [(C+1)][(C+1)]: weight-only factors;
-   T double [(C+1)][DV], partial double [2 * ceil((C+1) / 16)]: scratch; C + 1 <= 512.  Replaces ops.simple_layer_closed_form_wide's
-   dif_wide_gram_f64 -> GEMM -> GEMM -> dif_wide_scale_f64 chain (difformer.py:20-38 in closed form). */
+/* Float64 coefficients of that closed form (csrc/wide_coeffs.hip): record (dif_gram_sym_f32 / dif_gram128_f32) -> the operands
+   of the row GEMM x B + bias, B float [C][DV] = s R[0..C) and bias float [DV] = s R[C] + T[C], in two launches: T = G~ V~ with
+   G~ = [[X^T X, sx], [sx^T, n_global]] read straight from the record (lower blocks mirrored) and the partial norm products
+   <W~q^T W~q, G~> = |Q|^2, <W~k^T W~k, G~> = |K|^2; then R = P~ T with the scaling s = 1 / (|Q| |K|).  S double [2][(C+1)^2]
+   = {W~q^T W~q, W~k^T W~k}, V double [(C+1)][DV], P double [(C+1)][(C+1)]: weight-only factors; T double [(C+1)][DV],
+   partial double [2 * ceil((C+1) / 16)]: scratch; C + 1 <= 513 (difformer.py:20-38 in closed form). */
 int dif_wide_coeffs_f64(const float* record, int C, int64_t n_global, const double* S, const double* V, const double* P, int DV,
                         double* T, double* partial, float* B, float* bias, dif_stream_t stream);
 /* Closed-form `simple` layer at hidden 129..416 (image and text/run.sh:27 trains at 300, two lines at 400) in ONE pass over the
@@ -525,7 +514,7 @@ int dif_gram128_f32(const float* x, int64_t ldx, int64_t n_rows, int C, float* r
                     size_t workspace_bytes, dif_stream_t stream);
 /* Closed-form `simple` layer at hidden 65..128 (node classification/run.sh:42-44) in ONE pass over the rows
  * (csrc/simple_layer_wide.hip): out = LN(alpha (a_s (x Mn + cn) / (x.u + cd) + g_s ((A_hat x) Wv^T + (A_hat 1) bv^T) [+ x0]) +
- * (1 - alpha) x).  bmat [C][dv] / bias [dv] are dif_wide_scale_f64's outputs (columns [0, D) = Mn, column D = u; cn | cd);
+ * (1 - alpha) x).  bmat [C][dv] / bias [dv] are dif_wide_coeffs_f64's outputs (columns [0, D) = Mn, column D = u; cn | cd);
  * ax = A_hat x unscaled or NULL (no graph); Wv / bv / row_sums NULL together for use_weight = False (then C == D).  C, D <= 128,
  * multiples of 4, 16-byte aligned rows.  Both products run on split-bfloat16 operands (fp32 accumulation, ~4e-6). */
 int dif_simple_layer_wide_f32(const float* x, int64_t ldx, int64_t n_rows, int C, int D, const float* bmat, int dv,

@@ -1,6 +1,6 @@
 """Experiment: the long-row input Linear (512 -> 64 + LayerNorm + ReLU at CIFAR scale; difformer.py:188-191): split-bfloat16
-operands on the bf16 matrix core against the exact fp32-MFMA kernel (DIFFORMER_LINEAR_FP32_MFMA=1), time and error.
-    python scripts/exp_long_linear.py;  DIFFORMER_LINEAR_FP32_MFMA=1 python scripts/exp_long_linear.py"""
+operands on the bf16 matrix core against the exact fp32-MFMA kernel (DIFFORMER_EXACT_FP32=1), time and error.
+    python scripts/exp_long_linear.py;  DIFFORMER_EXACT_FP32=1 python scripts/exp_long_linear.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -31,6 +31,6 @@ for n, ci, co in ((50000, 512, 64), (30000, 512, 64), (15000, 512, 64), (8000, 5
         e.record(); torch.cuda.synchronize()
         ts.append(a.elapsed_time(e) / 20 * 1e3)
     byt = (n * ci + n * co) * 4
-    print(f"{'fp32 MFMA' if os.environ.get('DIFFORMER_LINEAR_FP32_MFMA') == '1' else 'split bf16'}: {n} x {ci} -> {co}: {min(ts):.1f} us "
+    print(f"{'fp32 MFMA' if os.environ.get('DIFFORMER_EXACT_FP32') == '1' else 'split bf16'}: {n} x {ci} -> {co}: {min(ts):.1f} us "
           f"({byt / min(ts) / 1e3:.0f} GB/s, {2 * n * ci * co / min(ts) / 1e6:.1f} TFLOP/s), max err / max|ref|: Linear {np.abs(raw - ref_raw).max() / np.abs(ref_raw).max():.2e}, "
           f"+ LayerNorm + ReLU {np.abs(out - ref).max() / np.abs(ref).max():.2e}", flush=True)

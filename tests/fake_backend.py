@@ -151,7 +151,7 @@ class OracleBackend:
 
     def simple_layer(self, x, coef, D, ax=None, Wv=None, bv=None, row_sums=None, gcn_scale=1.0, x0=None, residual=False,
                      alpha=0.5, ln_weight=None, ln_bias=None, eps=1e-5, relu=False, next_rowptr=None, next_plan=None,
-                     next_record=False, head=None, gather=None):
+                     head=None, gather=None):
         assert gather is None            # the in-kernel aggregation is the HIP backend's (ops checks for _simple_layer_gather)
         self.closed_form_calls = getattr(self, "closed_form_calls", 0) + 1
         xx, cf = _np(x).astype(np.float64), _np(coef).astype(np.float64)
@@ -177,7 +177,7 @@ class OracleBackend:
         if head is not None:                    # the model's output Linear in the same pass (difformer.py:208)
             z = z @ _np(head[0]).astype(np.float64).T + _np(head[1]).astype(np.float64)
         out = torch.from_numpy(z.astype(np.float32))
-        return out if (next_plan is None and not next_record) else (out, None, None)
+        return out if next_plan is None else (out, None)
 
     def row_order(self, rowptr, row_begin, n_rows):
         deg = np.diff(_np(rowptr).astype(np.int64))[row_begin: row_begin + n_rows]

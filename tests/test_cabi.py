@@ -23,9 +23,9 @@ def lib():
     return _lib.load()
 
 
-def test_header_declares_the_expected_entry_points():
+def test_header_declares_the_entry_points_of_abi_3():
     names = declared_functions()
-    assert "dif_simple_reduce_f32" in names and "dif_gcn_spmm_f32" in names and "dif_gcn_spmm_tail_f32" in names and "dif_project_reduce_f32" in names and "dif_linear_f32" in names and "dif_gcn_spmm_tail_bf16" in names and "dif_rowgemm_f32" in names and "dif_subgraph" in names and "dif_batched_simple_attn_f32" in names and "dif_row_order" in names and "dif_gcn_spmm_part_f32" in names and "dif_sliced_spmm_f32" in names and "dif_simple_layer_f32" in names and "dif_subgraph_batches_group" in names and "dif_graph_prepare" in names and "dif_gcn_edge_weight_grad_f32" in names and "dif_batched_sigmoid_attn_bwd_f32" in names and "dif_tiny_forward_f32" in names and "dif_tiny_backward_f32" in names and "dif_tiny_graph_build" in names and "dif_set_exact_fp32" in names and len(names) == 104
+    assert "dif_simple_reduce_f32" in names and "dif_gcn_spmm_f32" in names and "dif_gcn_spmm_tail_f32" in names and "dif_project_reduce_f32" in names and "dif_linear_f32" in names and "dif_gcn_spmm_tail_bf16" in names and "dif_rowgemm_f32" in names and "dif_subgraph" in names and "dif_batched_simple_attn_f32" in names and "dif_row_order" in names and "dif_gcn_spmm_part_f32" in names and "dif_sliced_spmm_f32" in names and "dif_simple_layer_f32" in names and "dif_subgraph_batches_group" in names and "dif_graph_prepare" in names and "dif_gcn_edge_weight_grad_f32" in names and "dif_batched_sigmoid_attn_bwd_f32" in names and "dif_tiny_forward_f32" in names and "dif_tiny_backward_f32" in names and "dif_tiny_graph_build" in names and "dif_set_exact_fp32" in names and len(names) == 101
 
 
 def test_library_exports_every_declared_symbol(lib):
@@ -48,8 +48,8 @@ def test_exact_fp32_switch_is_a_runtime_setting_of_the_library(lib):
         lib.dif_set_exact_fp32(was)
 
 
-def test_version_and_size_helpers(lib):
-    assert lib.dif_version() == 2
+def test_abi_3_version_and_size_helpers(lib):
+    assert lib.dif_version() == 3
     assert lib.dif_simple_reduced_len(1, 64, 64) == 64 * 64 + 64 + 64 + 2          # 4,226 floats
     assert lib.dif_simple_reduced_len(2, 16, 16) == 2 * (256 + 32) + 2
     assert lib.dif_simple_workspace_bytes(132534, 1, 64, 64) >= 4226 * 4

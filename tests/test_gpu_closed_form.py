@@ -198,9 +198,9 @@ def test_closed_form_layer_without_graph_matches_the_operator_path(dev):
 
 
 @pytest.mark.parametrize("n,deg,c", [(20000, 60, 64), (3000, 8, 32), (12345, 0, 64), (5000, 0, 32)])
-def test_layer_kernel_leaves_the_next_layers_products(n, deg, c, dev):
-    """want_next: the Gram record and the slice-major copy of the OUTPUT come out of the same pass and equal what
-    dif_gram_f32 computes from that output (copy bit for bit, record to fp32 rounding)."""
+def test_layer_kernel_leaves_the_next_layers_copy(n, deg, c, dev):
+    """want_next: the slice-major copy of the OUTPUT comes out of the same pass (from the layer kernel's registers) and equals,
+    bit for bit, what dif_gram_f32 writes from that output; the next layer's Gram record is computed fresh."""
     from difformer_amd import ops
     g = torch.Generator().manual_seed(n)
     x = torch.randn(n, c, generator=g).to(dev)
@@ -212,40 +212,22 @@ def test_layer_kernel_leaves_the_next_layers_products(n, deg, c, dev):
         ei = torch.cat([torch.randint(0, n, (2, n * deg), generator=g), torch.arange(n).repeat(2, 1)], dim=1).to(dev)
         csr = ops.csr_cache.get(ei, None, n, c * 4)
         sl = csr.sliced(0, n, c)
-    carry = {"want_next": True, "next_record": True}
+    carry = {"want_next": True}
     out = ops.simple_layer_closed_form(x, p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], csr, 1.0, 1.0, None, True, 0.5,
                                        lw, lb, 1e-5, carry=carry)
-    prod = carry["products"]
-    assert prod is not None and prod["x"] is out and prod["sl"] is sl
-    rec, ys = be.gram(out, csr.rowptr if sl is not None else None, sl.plan if sl is not None else None)
-    assert rel_err(prod["record"].cpu().numpy()[: c * c + c], rec.cpu().numpy()[: c * c + c]) < 1e-5
     if sl is not None:
-        assert torch.equal(prod["ys"], ys)
+        prod = carry["products"]
+        assert prod is not None and prod["x"] is out and prod["sl"] is sl
+        assert prod["record"] is None
+        assert torch.equal(prod["ys"], be.gram(out, csr.rowptr, sl.plan)[1])
     else:
-        assert prod["ys"] is None
-    # the cheaper default: only the copy comes out of the layer kernel (from its registers), the record is computed fresh
-    carry2 = {"want_next": True}
-    out2 = ops.simple_layer_closed_form(x, p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], csr, 1.0, 1.0, None, True, 0.5,
-                                        lw, lb, 1e-5, carry=carry2)
-    # (sparse graphs without the record: the layer kernel aggregates itself -- another summation order than the SpMM kernel's)
-    # (dense 64-column layers: the default kernel multiplies on split-bfloat16 operands, ~4e-6, the record-writing variant on the
-    # fp32 matrix core -- bit-equal only where both take the same products)
-    same_products = ops.EXACT_FP32 or c != 64
-    assert torch.equal(out2, out) if ((sl is not None or csr is None) and same_products) else rel_err(out2.cpu().numpy(), out.cpu().numpy()) < 2e-5
-    if sl is not None:
-        assert carry2["products"]["record"] is None
-        if same_products:
-            assert torch.equal(carry2["products"]["ys"], ys)
-        else:       # the copy of THIS pass's rows: bit for bit the slice-major copy dif_gram_f32 makes of out2
-            assert torch.equal(carry2["products"]["ys"], be.gram(out2, csr.rowptr, sl.plan)[1])
-    else:
-        assert carry2["products"] is None
+        assert carry["products"] is None           # no sliced product: no copy to leave (and no ys)
     # and the next layer uses them: same result as a fresh call without the carry
     a = ops.simple_layer_closed_form(out, p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], csr, 1.0, 1.0, None, True, 0.5,
                                      lw, lb, 1e-5, carry=carry)
     b = ops.simple_layer_closed_form(out, p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], csr, 1.0, 1.0, None, True, 0.5,
                                      lw, lb, 1e-5)
-    assert rel_err(a.cpu().numpy(), b.cpu().numpy()) < (1e-5 if same_products else 2e-5)
+    assert rel_err(a.cpu().numpy(), b.cpu().numpy()) < 1e-5
 
 
 class _EmulatedShard:
@@ -715,7 +697,7 @@ def test_gram_record_at_the_script_widths(n, c, dev):
 
 @pytest.mark.parametrize("C,D,n", [(300, 300, 5000), (68, 68, 3000), (128, 128, 4000), (400, 400, 6000), (132, 96, 5000),
                                    (512, 512, 4000)])
-def test_wide_coefficients_kernels_vs_float64_definition(C, D, n, dev):
+def test_wide_coefficients_kernel_vs_float64_restatement(C, D, n, dev):
     """dif_wide_coeffs_f64 (round 5: both float64 products of the wide closed form on own kernels) against the same algebra
     in float64 tensor ops, entry by entry -- the model-level parity metric barely sees [Mn | u] (the attention of the `simple`
     kernel is mean(V) + O(1 / N)), so the operands themselves are held to 1e-6 here."""
@@ -729,10 +711,17 @@ def test_wide_coefficients_kernels_vs_float64_definition(C, D, n, dev):
     co = ops.WideCoefficients(Wq, bq, Wk, bk, Wv, bv)
     rec = be.gram_sym(x)
     B, bias = be.wide_coeffs(rec, C, n, co.S, co.V, co.P)
-    Gt, partial = be.wide_gram(rec, C, n, co.S)
+    # the same algebra from the same record in float64 tensor ops: G~ with the lower 64-blocks mirrored, sum x and N appended
+    G = rec[: C * C].view(C, C).double()
+    blk = torch.arange(C, device=dev) // 64
+    G = torch.where(blk[:, None] <= blk[None, :], G, G.t())
+    sx = rec[C * C: C * C + C].double()
+    Gt = torch.cat([torch.cat([G, sx[:, None]], dim=1), torch.cat([sx, torch.tensor([float(n)], dtype=torch.float64, device=dev)])[None, :]])
+    q2, k2 = (co.S[0].view(C + 1, C + 1) * Gt).sum(), (co.S[1].view(C + 1, C + 1) * Gt).sum()
+    s0 = 1.0 / (q2.sqrt() * k2.sqrt())
     T = Gt @ co.V
     R = co.P @ T
-    B0, bias0 = be.wide_scale(R, T, partial, C)
+    B0, bias0 = (s0 * R[:C]).float(), (s0 * R[C] + T[C]).float()
     assert rel_err(B.cpu().numpy(), B0.cpu().numpy()) < 1e-6 and rel_err(bias.cpu().numpy(), bias0.cpu().numpy()) < 1e-6
     # and against the definition from x itself, in float64
     X = torch.cat([x.double(), torch.ones(n, 1, dtype=torch.float64, device=dev)], dim=1)
