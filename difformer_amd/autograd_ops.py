@@ -145,6 +145,7 @@ class _SigmoidAttention(torch.autograd.Function):
         width = max(q.shape[2], v.shape[2])
         ctx.hip = (q.dtype == torch.float32 and k.dtype == torch.float32 and v.dtype == torch.float32 and
                    (width <= 64 or (width <= 512 and not ops.EXACT_FP32)) and hasattr(be, "sigmoid_backward"))
+        ctx.planes = ctx.hip and width > 64          # the backward may take the plane kernels -- while exact mode stays off
         if ctx.hip:
             out, den = be.sigmoid_attention(q, k, v, want_den=True)
             ctx.save_for_backward(q, k, v, out, den)
@@ -156,7 +157,12 @@ class _SigmoidAttention(torch.autograd.Function):
     def backward(ctx, g):
         if ctx.hip:
             q, k, v, out, den = ctx.saved_tensors
-            dq, dk, dv = ops.get_backend().sigmoid_backward(q, k, v, out, den, g)
+            if ctx.planes and ops.EXACT_FP32:
+                # ops.set_exact_fp32(True) between forward and backward: the split-bfloat16 planes are no longer allowed
+                # (csrc/sigmoid_attn_bwd.hip refuses wide heads then) -- the tensor-op gradient of a forward made in exact mode
+                dq, dk, dv = _grad_by_recompute(_sigmoid_expr, (q, k, v), g.contiguous())
+            else:
+                dq, dk, dv = ops.get_backend().sigmoid_backward(q, k, v, out, den, g)
         else:
             dq, dk, dv = _grad_by_recompute(_sigmoid_expr, ctx.saved_tensors, g.contiguous())
         if ctx.shard is not None:

@@ -464,7 +464,7 @@ class DIFFormer(nn.Module):
         if len(convs) * (4.0 * x.shape[0] * hidden * x.element_size() + 8.0 * nnz) > _AUTO_GRAPH_MAX_BYTES:
             return None                  # GPU-bound: nothing to gain from a replay, gigabytes to hold for it
         key = [x.data_ptr(), x.shape, x.stride(), x.dtype, torch.cuda.current_stream(x.device).cuda_stream,
-               self.alpha, self.use_bn, self.residual, ops.SIDE_CHAIN, len(convs)]
+               self.alpha, self.use_bn, self.residual, ops.SIDE_CHAIN, ops.EXACT_FP32, len(convs)]
         lin = []
         for m in mods["fcs"]._modules.values():
             lin.append(m)

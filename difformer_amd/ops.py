@@ -970,8 +970,11 @@ CLOSED_FORM_WIDE_MIN = 128 if EXACT_FP32 else 64
 
 
 def set_exact_fp32(flag):
-    """Switch DIFFORMER_EXACT_FP32 at run time (bench.py's second pass) -> the previous setting.  Callers drop what they
-    cached under the old setting (`DIFFormer.invalidate_caches()`: a captured forward bakes the kernel choice in)."""
+    """Switch DIFFORMER_EXACT_FP32 at run time (bench.py's second pass) -> the previous setting.  What was made under the
+    old setting follows the switch by itself: a captured forward (DIFFormer's auto-graph) is keyed on it and runs eagerly,
+    then is captured afresh; the backward of a sigmoid head whose forward ran on the plane kernels takes the tensor-op
+    gradient once exact mode is on.  The packed weights and the weight-only factors of the closed form do not depend on it
+    (only the launchers that read them do), and CLOSED_FORM_WIDE_MIN below is read at every call."""
     global EXACT_FP32, CLOSED_FORM_WIDE_MIN
     was = EXACT_FP32
     EXACT_FP32 = bool(flag)
