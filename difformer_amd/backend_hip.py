@@ -945,15 +945,21 @@ class HipBackend:
         rc = self.lib.dif_sliced_plan(int(n_src), int(n_rows), int(F), plan)
         return plan if rc == 0 else None
 
-    def sliced_build(self, rowptr, blkptr, src, n_src, nnz, row_begin, n_rows, F, plan, order=None, parts=None, n_pos=None):
+    def sliced_build(self, rowptr, blkptr, src, n_src, nnz, row_begin, n_rows, F, plan, order=None, parts=None, n_pos=None,
+                     quad_cap=1):
         """-> (entries uint16 [512 * n_blocks], table int32) or None when a (row position, tile) group exceeds the 16-bit
         counters.  order: the shard's rows by descending degree (row_order) for skewed graphs, None = natural order;
         parts (uint16 [n_pos], with order int32 [n_pos]): hub rows split into lock-step parts (include/difformer_hip.h,
-        "row positions"); plan = sliced_plan(n_src, n_pos, F).  Two host syncs (status, block count): cold path, once
-        per (graph, shard, F)."""
+        "row positions"); plan = sliced_plan(n_src, n_pos, F).  quad_cap: lanes of a hardware lane group that may read
+        one bank quad in a step (1 = strict, conflict-free schedule; 2 = packed); it goes to the two build calls in bits
+        16-17 of plan[0] of a private copy of the plan (include/difformer_hip.h), the caller's plan stays as it is.
+        Two host syncs (status, block count): cold path, once per (graph, shard, F)."""
         dev = _require_device(rowptr, blkptr, src, order, parts)
         n_pos = int(n_rows) if n_pos is None else int(n_pos)
         slices, panels, G, PW, W, R, T, NT = (int(v) for v in plan)
+        if not 1 <= int(quad_cap) <= 4:
+            raise ValueError(f"difformer_amd: quad_cap={quad_cap!r}: expected 1 (strict) or 2 (packed)")
+        plan = (ctypes.c_int32 * 8)(slices | (int(quad_cap) - 1) << 16, panels, G, PW, W, R, T, NT)
         i32 = dict(dtype=torch.int32, device=dev)
         srt = torch.empty(max(int(nnz), 1), dtype=torch.int16, device=dev)
         counts = torch.empty(n_pos * NT * 32, dtype=torch.uint8, device=dev)

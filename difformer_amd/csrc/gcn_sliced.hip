@@ -21,7 +21,10 @@
 //     one (no register rotation -> counted vmcnt waits);
 //   * inside a (tile, round) the entries of the 16 lanes that share an LDS cycle of ds_read_b128 are scheduled at build
 //     time (greedy edge colouring) so that they hit 16 different bank quads: no bank conflicts (SQ_LDS_BANK_CONFLICT
-//     = 0); idle slots read one of 16 zero rows, also on a free quad.  Random order costs 1.6x.
+//     = 0); idle slots read one of 16 zero rows, also on a free quad.  Random order costs 1.6x.  Large near-uniform
+//     graphs take the PACKED schedule instead (same format, same sweep): slots of rows with equal per-tile block counts
+//     and up to TWO lanes of the 16 on a quad -- 1.25 instead of 1.56 padded lane-steps per entry at C4 for 0.38
+//     conflict cycles per wave-step, 0.31 ms per launch (profiles/r07_experiments.md).
 // The same adjacency slice is swept by the 16 slice-workgroups of a panel, which sit on one XCD (block b -> XCD b % 8),
 // so the entry stream comes from HBM once.
 // Measured at C4 (79.3 M entries): 0.33 ms per launch against 1.12 ms (profiles/r02_experiments.md).
@@ -252,6 +255,11 @@ __global__ __launch_bounds__(256) void sliced_sort_kernel(const int32_t* __restr
 // in rotating order; a lane takes the bank quad it still has the most entries on among the quads no earlier lane of the
 // step took (within ~0.2 % of the lower bound max(longest lane, fullest quad)).  EMIT = false only counts the steps;
 // EMIT = true writes the schedule of every step as a 16-byte record into the block it belongs to.
+// cap = 2 (the PACKED schedule, asked for in the plan record, plan_quad_cap): up to two lanes of a step may take the same quad -- the
+// hardware serialises them at one extra LDS cycle for the group -- which lowers the bound to max(longest lane,
+// ceil(fullest quad / 2)).  Sharing is kept to the cells that need it (see the lane loop); a lane that idles still
+// reads a zero row on a quad NO lane of the step uses (distinct quads in use <= active lanes, so there are enough).
+// cap = 1 is the strict schedule, bit for bit what this kernel built before it had the argument.
 // The 16 x 16 remaining counts (16-bit, two per dword) live in 128 REGISTERS: the lane loop is unrolled twice (lanes
 // >= start, then lanes < start; start = step & 15 is wave-uniform, the skipped bodies cost a scalar branch) so that every
 // register index is static.  There are only ~1,700 waves of this work at C4, so occupancy does not matter and the
@@ -263,7 +271,8 @@ __global__ __launch_bounds__(256) void sliced_sort_kernel(const int32_t* __restr
 constexpr int kColorThreads = 64;
 
 template <bool EMIT>
-__global__ __launch_bounds__(kColorThreads) void sliced_color_kernel(int64_t n_pos, Plan pl, const uint4* __restrict__ cnt,
+__global__ __launch_bounds__(kColorThreads) void sliced_color_kernel(int64_t n_pos, Plan pl, int cap,
+                                                                     const uint4* __restrict__ cnt,
                                                                      int32_t* __restrict__ len,
                                                                      const int32_t* __restrict__ tab,
                                                                      uint16_t* __restrict__ ell) {
@@ -273,20 +282,44 @@ __global__ __launch_bounds__(kColorThreads) void sliced_color_kernel(int64_t n_p
     const int grp = static_cast<int>(gid & 3);
     const int t = static_cast<int>((gid >> 2) % pl.NT);
     const int64_t g = (gid >> 2) / pl.NT;                     // slot
+    const bool packed = cap > 1;                 // kernel-uniform
     uint32_t c[16][8];                           // c[lane][k]: entries left on quads 2k (low half) and 2k + 1 (high half)
+    uint32_t col[16];                            // packed: entries left on quad q over the 16 lanes (its column)
+    int rem[16];                                 // packed: entries left of lane i (its row)
     int remaining = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) col[q] = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int64_t pos = g * 64 + kLaneOf[grp * 16 + i];
         Counts cc = {{0, 0, 0, 0}};
         if (pos < n_pos) cc = load_counts(cnt, pos * pl.NT + t);
+        rem[i] = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             c[i][2 * k] = static_cast<uint32_t>(cc.w[k]);
             c[i][2 * k + 1] = static_cast<uint32_t>(cc.w[k] >> 32);
-            remaining += static_cast<int>((cc.w[k] & 0xffffu) + ((cc.w[k] >> 16) & 0xffffu) + ((cc.w[k] >> 32) & 0xffffu) +
-                                          (cc.w[k] >> 48));
+            const uint32_t q0 = cc.w[k] & 0xffffu, q1 = (cc.w[k] >> 16) & 0xffffu, q2 = (cc.w[k] >> 32) & 0xffffu,
+                           q3 = static_cast<uint32_t>(cc.w[k] >> 48);
+            col[4 * k] += q0; col[4 * k + 1] += q1; col[4 * k + 2] += q2; col[4 * k + 3] += q3;
+            rem[i] += static_cast<int>(q0 + q1 + q2 + q3);
         }
+        remaining += rem[i];
+    }
+    // packed: the length to aim for -- max(longest lane, ceil(fullest quad / cap)) over the four lane groups of the
+    // (slot, tile), which are four neighbouring threads, rounded up to whole blocks: the round is that long anyway, so
+    // a quad is shared only where the round could otherwise not end there.  Both runs derive the same target from the
+    // same counts, so the steps they take are the same.
+    int target = 0;
+    if (packed) {
+        int longest = 0;
+        uint32_t fullest = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { longest = max(longest, rem[i]); fullest = max(fullest, col[i]); }
+        target = max(longest, static_cast<int>((fullest + cap - 1) / cap));
+        target = max(target, __shfl_xor(target, 1));
+        target = max(target, __shfl_xor(target, 2));
+        target = (target + kSteps - 1) / kSteps * kSteps;
     }
     // where this slot's blocks go
     const int j = static_cast<int>(g / pl.PW);
@@ -318,30 +351,53 @@ __global__ __launch_bounds__(kColorThreads) void sliced_color_kernel(int64_t n_p
     int step = 0;
     while (remaining > 0) {
         new_row(step);
-        uint32_t used = 0, picked = 0, qlo = 0, qhi = 0;
+        // used: quads taken in this step; full: quads that take no further lane (packed: taken cap = 2 times)
+        uint32_t used = 0, full = 0, picked = 0, qlo = 0, qhi = 0;
         const int start = step & 15;
+        const int left = target - step;              // packed: steps left inside the target, this one included
 #pragma unroll
         for (int pass = 0; pass < 2; ++pass) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 if ((i >= start) != (pass == 0)) continue;
-                // most entries left among the free quads; ties go to the lower quad (key = count << 4 | 15 - quad)
-                uint32_t key = 0;
+                // strict: most entries left among the free quads; ties go to the lower quad (key = count << 4 | 15 - quad).
+                // packed: the count in the key is the quad's COLUMN (the fullest column is the one that bounds the
+                // round); a quad one lane has taken is a candidate too while its column still holds more entries than
+                // steps remain after this one (kshare: it has to be shared in some step anyway) and wins only against
+                // emptier free quads; a lane that has no step to spare shares whatever quad is not full (kany).
+                uint32_t key = 0, kshare = 0, kany = 0;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    const uint32_t lo = ((c[i][k] & 0xffffu) << 4) | static_cast<uint32_t>(15 - 2 * k);
-                    const uint32_t hi = ((c[i][k] >> 16) << 4) | static_cast<uint32_t>(14 - 2 * k);
-                    const uint32_t flo = ((used >> (2 * k)) & 1u) ? 0u : lo;
-                    const uint32_t fhi = ((used >> (2 * k + 1)) & 1u) ? 0u : hi;
-                    key = max(key, max(flo, fhi));
+                    const uint32_t olo = c[i][k] & 0xffffu, ohi = c[i][k] >> 16;
+                    const uint32_t wlo = packed ? col[2 * k] : olo, whi = packed ? col[2 * k + 1] : ohi;
+                    const uint32_t lo = olo ? ((wlo << 4) | static_cast<uint32_t>(15 - 2 * k)) : 0u;
+                    const uint32_t hi = ohi ? ((whi << 4) | static_cast<uint32_t>(14 - 2 * k)) : 0u;
+                    const bool ulo = (used >> (2 * k)) & 1u, uhi = (used >> (2 * k + 1)) & 1u;
+                    key = max(key, max(ulo ? 0u : lo, uhi ? 0u : hi));
+                    if (packed) {
+                        const uint32_t slo = (ulo && !((full >> (2 * k)) & 1u)) ? lo : 0u;
+                        const uint32_t shi = (uhi && !((full >> (2 * k + 1)) & 1u)) ? hi : 0u;
+                        kany = max(kany, max(slo, shi));
+                        kshare = max(kshare, max(static_cast<int>(col[2 * k]) >= left ? slo : 0u,
+                                                 static_cast<int>(col[2 * k + 1]) >= left ? shi : 0u));
+                    }
                 }
-                if (key < 16u) continue;                       // nothing left on a free quad
+                bool share = false;
+                if (packed) {
+                    if (kshare > key) { key = kshare; share = true; }
+                    else if (key < 16u && rem[i] >= left && kany >= 16u) { key = kany; share = true; }
+                }
+                if (key < 16u) continue;                       // nothing left on a quad this lane may take
                 const uint32_t best = 15u - (key & 15u);
-                used |= 1u << best;
+                if (share) full |= 1u << best;
+                else used |= 1u << best;
                 picked |= 1u << i;
                 const uint32_t dec = 1u << (16u * (best & 1u)), wsel = best >> 1;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) c[i][k] -= (wsel == static_cast<uint32_t>(k)) ? dec : 0u;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) col[q] -= (best == static_cast<uint32_t>(q)) ? 1u : 0u;
+                --rem[i];
                 --remaining;
                 if (EMIT) {
                     if (i < 8) qlo |= best << (4 * i);
@@ -830,13 +886,19 @@ int check_positions(const int32_t* row_order, const uint16_t* parts, int64_t n_r
     return 0;
 }
 
+// The schedule rides in the plan record: plan[0] = F / 4 (<= 256) in its low 16 bits and the quad capacity - 1 in bits
+// 16-17 (0 as dif_sliced_plan writes it: the strict schedule).  Only the two build calls look at the capacity.
+constexpr int32_t kPlanSlicesMask = 0xffff, kPlanCapMask = 0x30000;
+int plan_quad_cap(const int32_t* plan) { return ((plan[0] & kPlanCapMask) >> 16) + 1; }
+
 int check_plan(const int32_t* plan, int64_t n_src, int64_t n_rows, int F, Plan& pl) {
     if (!plan) return dif::fail(DIF_E_BADARG, "dif_sliced: plan is null");
     Plan want;
     const int rc = make_plan(n_src, n_rows, F, want);
     if (rc) return dif::fail(rc, "dif_sliced: shape not covered (n_src=%lld, n_rows=%lld, F=%d)",
                              static_cast<long long>(n_src), static_cast<long long>(n_rows), F);
-    pl = Plan{plan[0], plan[1], plan[2], plan[3], plan[4], plan[5], plan[6], plan[7], want.S};
+    pl = Plan{plan[0] & kPlanSlicesMask, plan[1], plan[2], plan[3], plan[4], plan[5], plan[6], plan[7], want.S};
+    if ((plan[0] & ~(kPlanSlicesMask | kPlanCapMask)) != 0) pl.slices = -1;      // unknown bits: reported as a mismatch below
     if (pl.slices != want.slices || pl.panels != want.panels || pl.G != want.G || pl.PW != want.PW || pl.W != want.W ||
         pl.R != want.R || pl.T != want.T || pl.NT != want.NT)
         return dif::fail(DIF_E_BADARG, "dif_sliced: plan does not match dif_sliced_plan(n_src, n_rows, F)");
@@ -869,6 +931,8 @@ extern "C" int dif_sliced_measure(const int32_t* rowptr, const int32_t* blkptr, 
     Plan pl;
     if (int rc = check_positions(row_order, parts, n_rows, n_pos, "dif_sliced_measure")) return rc;
     if (int rc = check_plan(plan, n_src, n_pos, F, pl)) return rc;
+    const int quad_cap = plan_quad_cap(plan);
+    DIF_REQUIRE(quad_cap <= 2, DIF_E_BADARG, "dif_sliced_measure: the plan's quad capacity must be 1 (strict) or 2 (packed)");
     DIF_REQUIRE(row_begin >= 0 && row_begin + n_rows <= n_src && nnz >= 0, DIF_E_BADARG, "dif_sliced_measure: bad row range");
     DIF_REQUIRE(rowptr && (nnz == 0 || src) && sorted && counts && lengths && table && status, DIF_E_BADARG,
                 "dif_sliced_measure: null pointer");
@@ -884,7 +948,8 @@ extern "C" int dif_sliced_measure(const int32_t* rowptr, const int32_t* blkptr, 
     if (int rc = dif::launch_status("sliced_sort_kernel")) return rc;
     const int64_t n_hw = static_cast<int64_t>(pl.G) * pl.NT * 4;
     hipLaunchKernelGGL((sliced_color_kernel<false>), dim3(static_cast<unsigned>((n_hw + kColorThreads - 1) / kColorThreads)),
-                       dim3(kColorThreads), 0, st, n_pos, pl, static_cast<const uint4*>(counts), lengths, nullptr, nullptr);
+                       dim3(kColorThreads), 0, st, n_pos, pl, quad_cap, static_cast<const uint4*>(counts), lengths, nullptr,
+                       nullptr);
     if (int rc = dif::launch_status("sliced_color_kernel")) return rc;
     hipLaunchKernelGGL(sliced_table_kernel, dim3(1), dim3(1024), 0, st, lengths, pl, table);
     return dif::launch_status("sliced_table_kernel");
@@ -897,6 +962,8 @@ extern "C" int dif_sliced_emit(const int32_t* rowptr, const int32_t* blkptr, int
     Plan pl;
     if (int rc = check_positions(row_order, parts, n_rows, n_pos, "dif_sliced_emit")) return rc;
     if (int rc = check_plan(plan, n_src, n_pos, F, pl)) return rc;
+    const int quad_cap = plan_quad_cap(plan);
+    DIF_REQUIRE(quad_cap <= 2, DIF_E_BADARG, "dif_sliced_emit: the plan's quad capacity must be 1 (strict) or 2 (packed)");
     DIF_REQUIRE(rowptr && sorted && counts && table && entries && n_blocks >= 1, DIF_E_BADARG, "dif_sliced_emit: null pointer");
     DIF_REQUIRE(pl.NT == 1 || blkptr, DIF_E_BADARG, "dif_sliced_emit: more than one tile needs blkptr");
     DIF_REQUIRE(dif::aligned16(entries) && dif::aligned16(counts), DIF_E_BADARG,
@@ -904,7 +971,8 @@ extern "C" int dif_sliced_emit(const int32_t* rowptr, const int32_t* blkptr, int
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n_hw = static_cast<int64_t>(pl.G) * pl.NT * 4;
     hipLaunchKernelGGL((sliced_color_kernel<true>), dim3(static_cast<unsigned>((n_hw + kColorThreads - 1) / kColorThreads)),
-                       dim3(kColorThreads), 0, st, n_pos, pl, static_cast<const uint4*>(counts), nullptr, table, entries);
+                       dim3(kColorThreads), 0, st, n_pos, pl, quad_cap, static_cast<const uint4*>(counts), nullptr, table,
+                       entries);
     if (int rc = dif::launch_status("sliced_color_kernel")) return rc;
     const int64_t n_st = static_cast<int64_t>(pl.G) * pl.NT;                 // one wave per (slot, tile)
     hipLaunchKernelGGL(sliced_fill_kernel, dim3(static_cast<unsigned>((n_st + 3) / 4)), dim3(256), 0, st, rowptr, blkptr,
@@ -919,7 +987,7 @@ extern "C" int dif_sliced_prescale_f32(const float* x, int64_t ldx, const int32_
                 "dif_sliced_prescale: bad argument");
     DIF_REQUIRE(ldx % 4 == 0 && dif::aligned16(x) && dif::aligned16(ys), DIF_E_BADARG,
                 "dif_sliced_prescale: x rows and ys must be 16-byte aligned");
-    const int slices = plan[0];
+    const int slices = plan[0] & kPlanSlicesMask;
     const int64_t npad = static_cast<int64_t>(plan[6]) * plan[7];
     DIF_REQUIRE(slices == F / 4 && npad >= n_src, DIF_E_BADARG, "dif_sliced_prescale: plan does not match F / n_src");
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -192,15 +192,54 @@ SLICED_SPLIT_FACTOR = 4.0   # rows beyond this multiple of the mean degree are s
 SLICED_MAX_PARTS = 64       # one slot
 
 
+# Two schedules of the format.  strict: natural row order, no two lanes of a hardware lane group on
+# one bank quad in a step.  packed (near-uniform degrees only): rows with equal per-tile block counts share a slot and a
+# quad may be read by two lanes of a step -- fewer padded steps for a few 2-way shared LDS reads, a longer cold build.
+# DIFFORMER_SLICED_SCHEDULE = strict | packed | auto (default); auto packs where the build is paid back within 64
+# launches (one short training run, or a few evaluations of a 4-layer model).  Measured on the MI355X at F = 64
+# (profiles/r07_experiments.md): a launch saves
+#    2.4 M entries: 1.4 us    10 M: 8 us    30 M: 15 us    79 M (headline): 42 us        (scripts/exp_slot_order.py)
+# and the cold build of CSR + format, as `bench.py --full` times it on the headline graph, goes from 8.0 to 9.9 ms
+# (the slot order's sort, the indirection through `order`, their host side; back to back in one warm process the
+# format build alone differs by 0.55-0.75 ms at every size).  1.9 ms / 64 = 30 us per launch: between the 30 M and
+# the 79 M point, ~57 M entries by interpolation.
+SLICED_PACKED_MIN_ENTRIES = 60_000_000
+SLICED_PACKED_MAX_TILES = 40  # the slot order's key holds one bit per tile in an int64
+
+
+def sliced_schedule():
+    mode = os.environ.get("DIFFORMER_SLICED_SCHEDULE", "auto").strip().lower() or "auto"
+    if mode not in ("strict", "packed", "auto"):
+        raise ValueError(f"DIFFORMER_SLICED_SCHEDULE={mode!r}: expected strict, packed or auto")
+    return mode
+
+
+def packed_slot_order(rowptr, blkptr, n_src, NT, row_begin, n_rows):
+    """Rows of a near-uniform graph in the order that forms the slots of the packed schedule: by the largest per-tile
+    block count (8-step blocks, descending), then by the set of tiles that reach it, stable -- the 64 lock-step rows of
+    a slot then end their rounds in the same block in (nearly) every tile.  int32 [n_rows], on the device."""
+    if NT > 1:
+        cnt = blkptr.view(NT + 1, n_src)[:, row_begin: row_begin + n_rows]
+        blocks = (cnt[1:] - cnt[:-1] + 7) // 8
+    else:
+        blocks = ((rowptr[row_begin + 1: row_begin + n_rows + 1] - rowptr[row_begin: row_begin + n_rows] + 7) // 8)[None, :]
+    top = blocks.max(dim=0).values.to(torch.int64)
+    weights = torch.ones(NT, dtype=torch.int64, device=blocks.device) << torch.arange(NT, device=blocks.device)
+    hot = ((blocks == top[None, :]).to(torch.int64) * weights[:, None]).sum(dim=0)
+    key = (top.max() - top) * (1 << NT) + hot
+    return torch.argsort(key, stable=True).to(torch.int32)
+
+
 class SlicedAdjacency:
     """Entry blocks + table + geometry of the feature-sliced product (include/difformer_hip.h, dif_sliced_*).
-    order: rows by descending degree (skewed graphs); parts / n_pos: hub rows split into lock-step parts ("row
-    positions" in the header) -- then order has n_pos entries (-1 = padding) and plan is the geometry of n_pos positions;
+    order: rows by descending degree (skewed graphs) or by tile profile (packed schedule); parts / n_pos: hub rows split
+    into lock-step parts ("row positions" in the header) -- then order has n_pos entries (-1 = padding) and plan is the
+    geometry of n_pos positions; quad_cap: 1 = strict schedule, 2 = packed.
     The slice-major source copy is written with the same plan (its tiling)."""
 
-    def __init__(self, plan, entries, table, order=None, parts=None, n_pos=None):
+    def __init__(self, plan, entries, table, order=None, parts=None, n_pos=None, quad_cap=1):
         self.plan, self.entries, self.table, self.order = plan, entries, table, order
-        self.parts, self.n_pos = parts, n_pos
+        self.parts, self.n_pos, self.quad_cap = parts, n_pos, int(quad_cap)
 
 
 def split_positions(deg_sorted, order, cap, max_parts=SLICED_MAX_PARTS):
@@ -310,6 +349,8 @@ class GraphCSR:
         deg = self.rowptr[row_begin + 1: row_begin + n_rows + 1] - self.rowptr[row_begin: row_begin + n_rows]
         max_deg, total = (int(v) for v in torch.stack([deg.max(), deg.sum()]).tolist())       # one sync, cold path
         order = parts = n_pos = None
+        quad_cap = 1
+        mode = sliced_schedule()
         if max_deg * n_rows > 2 * total:
             order = be.row_order(self.rowptr, row_begin, n_rows)[0]
             cap = max(int(SLICED_SPLIT_FACTOR * total / n_rows), 64)
@@ -319,11 +360,14 @@ class GraphCSR:
                 plan = be.sliced_plan(self.num_nodes, n_pos, F)
                 if plan is None or int(plan[6]) != T or int(plan[7]) != NT:
                     return None
+        elif NT <= SLICED_PACKED_MAX_TILES and (mode == "packed" or (mode == "auto" and total >= SLICED_PACKED_MIN_ENTRIES)):
+            order = packed_slot_order(self.rowptr, self.blkptr, self.num_nodes, NT, row_begin, n_rows)
+            quad_cap = 2
         built = be.sliced_build(self.rowptr, self.blkptr, self.src, self.num_nodes, self.nnz, row_begin, n_rows, F, plan, order,
-                                parts, n_pos)
+                                parts, n_pos, quad_cap)
         if built is None:
             return None
-        return SlicedAdjacency(plan, built[0], built[1], order, parts, n_pos)
+        return SlicedAdjacency(plan, built[0], built[1], order, parts, n_pos, quad_cap)
 
     def row_sums(self):
         """A_hat 1 (float32 [N]): what the bias of the value projection turns into under the aggregation,

@@ -304,6 +304,16 @@ int dif_simple_layer_f32(const float* x, int64_t ldx, int64_t n_rows, int C, int
  *   dif_sliced_emit     writes the blocks: `entries` uint16[512 * n_blocks] with n_blocks = table[(R+1)*panels*NT*waves]
  *                       (read back by the caller: the size is data dependent).  sorted / counts / lengths may be freed
  *                       afterwards; entries + table + plan (+ row_order) are the format.
+ *   quad capacity       The schedule of a build rides in the plan record: bits 16-17 of plan[0] hold the QUAD CAPACITY
+ *                       - 1, how many of the 16 lanes that share an LDS cycle may read the same bank quad in one step
+ *                       (plan[0] & 0xffff stays F/4).  0, as dif_sliced_plan writes it: capacity 1, the strict
+ *                       (conflict-free) schedule.  1: capacity 2, the packed schedule -- a round is as long as
+ *                       max(longest row, ceil(fullest quad column / 2)) instead of max(longest row, fullest column), and
+ *                       the hardware serialises the shared quads (one extra LDS cycle of the lane group per step that
+ *                       shares).  It pays together with a row_order that puts rows of equal per-tile block counts into
+ *                       one slot (near-uniform degrees).  dif_sliced_measure and dif_sliced_emit of one build take the
+ *                       same value; larger capacities: DIF_E_BADARG.  dif_sliced_prescale_f32 and dif_sliced_spmm_f32
+ *                       ignore the bits (the format is the same); every other call takes the plan without them.
  *   dif_sliced_prescale_f32  ys float[F/4][T*NT][4] = deg^-1/2 (0 for a node without incoming entries, :74) times x,
  *                       slice-major; x holds all n_src rows.
  *   dif_sliced_spmm_f32 out[r,:] = gcn_scale * deg[r]^-1/2 * sum_e ys[src_e] (+ attn_scale * attn[r,:]) for the n_rows

@@ -3,7 +3,9 @@ format of csrc/gcn_sliced.hip spends on the C4 graph under different assignments
     python scripts/exp_sliced_slots.py            -> profiles/r06_sliced_slots.txt (table quoted in profiles/r06_experiments.md)
 Format rules restated from csrc/gcn_sliced.hip: a (panel, wave) pair owns R slots (rounds; snake deal over the pairs); per source
 tile a round is as long as its longest row, in blocks of 8 steps; within a pair the round lengths are padded to a non-increasing
-sequence (round 0 the longest); every lane of a slot steps through the slot's blocks (lock step)."""
+sequence (round 0 the longest); every lane of a slot steps through the slot's blocks (lock step).
+    python scripts/exp_sliced_slots.py --packed   -> profiles/r07_sliced_slots.txt only: slot order x column rule x quad capacity
+(the trade the packed schedule makes: padded steps against 2-way shared bank quads, profiles/r07_experiments.md)."""
 import sys
 import numpy as np
 
@@ -45,6 +47,52 @@ def steps(order, quads=False):
         tot += int(r.sum()) * 8 * 64
     return tot
 
+
+def packed_steps(order, rule):
+    """(padded lane-steps, shared cells) when a round of a (slot, tile) is rule(longest row, fullest bank-quad column) steps long,
+    columns taken per 16-row hardware lane group.  Shared cells: what does not fit a column of K cells, sum max(0, column - K) --
+    each one is a second read of a quad in its step, one extra LDS cycle of the lane group."""
+    pad = np.full(G * 64, -1, dtype=np.int64)
+    pad[:N] = order
+    c = np.where(pad[:, None, None] >= 0, c3[np.clip(pad, 0, N - 1)], 0).reshape(G, 64, NT, 16)[:, LANE_OF].reshape(G, 4, 16, NT, 16)
+    row = c.sum(axis=4).max(axis=(1, 2))                          # [slot, tile]
+    col = c.sum(axis=2)                                           # [slot, group, tile, quad]
+    nb = -(-rule(row, col.max(axis=(1, 3))) // 8)
+    tot = 0
+    fin = np.zeros_like(nb)
+    for pw in range(PW):
+        ss = [j * PW + (PW - 1 - pw if j & 1 else pw) for j in range(R)]
+        r = np.stack([nb[s] if s < G else np.zeros(NT, dtype=nb.dtype) for s in ss])
+        r = np.maximum.accumulate(r[::-1], axis=0)[::-1]
+        for j, s in enumerate(ss):
+            if s < G:
+                fin[s] = r[j]
+        tot += int(r.sum()) * 8 * 64
+    shared = int(np.maximum(col - (fin * 8)[:, None, :, None], 0).sum())
+    return tot, shared
+
+
+# lanes that share one LDS cycle of ds_read_b128: position -> lane (kLaneOf of csrc/gcn_sliced.hip)
+LANE_OF = np.array([0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27, 4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31,
+                    32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59, 36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63])
+if "--packed" in sys.argv:
+    blk = -(-cnt // 8)
+    top = blk.max(axis=1)
+    hot = ((blk == top[:, None]) * (1 << np.arange(NT)).astype(np.int64)).sum(axis=1)
+    orders = (("natural order", np.arange(N)), ("tile-profile order", np.lexsort((hot, -top))))
+    rules = (("max(longest row, fullest column)   [strict]", lambda r, c: np.maximum(r, c)),
+             ("max(row, column - 8)", lambda r, c: np.maximum(r, c - 8)),
+             ("max(row, column - 12)", lambda r, c: np.maximum(r, c - 12)),
+             ("max(longest row, ceil(fullest column / 2))   [packed]", lambda r, c: np.maximum(r, -(-c // 2))))
+    with open("profiles/r07_sliced_slots.txt", "w") as f:
+        f.write(f"# C4 synthetic graph: {N} rows, {nnz} entries, {NT} source tiles, {G} slots of 64 rows, plan {PW} pairs x {R} rounds\n")
+        f.write("# lane-steps per entry | shared cells | extra LDS cycles per wave-step (a conflict-free step = 4) | slots formed by | round length\n")
+        for oname, o in orders:
+            for rname, rule in rules:
+                tot, shared = packed_steps(o, rule)
+                f.write(f"{tot / nnz:7.3f}  {shared:9d}  {shared / (tot / 64):6.3f}  {oname:20s} {rname}\n")
+    print(open("profiles/r07_sliced_slots.txt").read())
+    sys.exit(0)
 
 deg = cnt.sum(axis=1)
 rows = np.arange(N)
