@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -58,6 +59,13 @@ def _f32(t, name):
     return t
 
 
+def _all_f32(**named):
+    """Every operand that is given (not None) must be float32; the keyword is the name in the message."""
+    for name, t in named.items():
+        if t is not None and t.dtype != torch.float32:
+            _f32(t, name)
+
+
 _SUFFIX = {torch.float32: "f32", torch.bfloat16: "bf16"}
 
 
@@ -92,8 +100,61 @@ def _row_major(t, width):
     return t, int(ld)
 
 
+def _rows(t, width, align=False):
+    """_row_major of an optional operand: None -> (None, 0).  align: the kernel reads the rows four elements at a time,
+    so a leading dimension that is no multiple of 4 elements, or a first row that does not start on a 4-element
+    boundary, is replaced by a dense copy."""
+    if t is None:
+        return None, 0
+    t, ld = _row_major(t, width)
+    if align and (ld % 4 or t.data_ptr() % (4 * t.element_size())):
+        return t.contiguous(), width
+    return t, ld
+
+
+def _contig(*tensors, f32=None):
+    """The operands made contiguous, None staying None; f32: the name under which each must also be float32."""
+    if f32 is not None:
+        for t in tensors:
+            if t is not None and t.dtype != torch.float32:
+                _f32(t, f32)
+    return [None if t is None else t.contiguous() for t in tensors]
+
+
+def _workspace(nbytes, dev, floor=0, or_none=False):
+    """Scratch bytes of one call.  floor: allocate at least that much (the kernel is handed an address even when it asks
+    for nothing); or_none: no buffer at all when the kernel asks for nothing."""
+    if or_none and not nbytes:
+        return None
+    return torch.empty(max(nbytes, floor), dtype=torch.uint8, device=dev)
+
+
+def _slice_major(F, plan, dev):
+    """ys [F/4, T*NT, 4]: the slice-major copy of [n, F] rows that sliced_spmm reads (plan: sliced_plan's geometry)."""
+    return torch.empty((F // 4, int(plan[6]) * int(plan[7]), 4), dtype=torch.float32, device=dev)
+
+
+def _check_edge_index(edge_index):
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise TypeError("difformer_amd: edge_index must be an int64 tensor of shape [2, E]")
+
+
+def _kept_status(dev):
+    """int64 [2] = [kept count | status word] that a filtering kernel fills -> (both, count, status): ONE read-back."""
+    res = torch.zeros(2, dtype=torch.int64, device=dev)
+    return res, res[:1], res[1:].view(torch.int32)
+
+
+def _read_kept(res, ids, num_nodes):
+    """Kept count of _kept_status after the call; raises when the status word reports node ids (`ids`) out of range."""
+    kept, bad = res.tolist()                                # one sync: the result size is data dependent
+    if bad & 0xFFFFFFFF:
+        raise IndexError(f"difformer_amd: {ids} node ids outside [0, {num_nodes})")
+    return kept
+
+
 class _Timed:
-    """Optional HIP-event bracket around one C-ABI call (events on the launching stream)."""
+    """HIP-event bracket around one C-ABI call (events on the launching stream): the slow path of HipBackend._call."""
 
     def __init__(self, backend, name, dev):
         only = backend.kernel_events_only          # bracket just these entry points (keeps the host ahead of the GPU)
@@ -119,24 +180,6 @@ class _Timed:
         return self.ctx.__exit__(*exc) if self.ctx is not None else False
 
 
-class _NoBracket:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NO_BRACKET = _NoBracket()
-
-
-def _timed(backend, name, dev):
-    """The common case -- no event collection, operands on the current device -- costs one shared no-op context."""
-    if backend.kernel_events is None and dev.index is not None and torch.cuda.current_device() == dev.index:
-        return _NO_BRACKET
-    return _Timed(backend, name, dev)
-
-
 class HipBackend:
     has_tiny = True          # the whole-model kernels for tiny graphs (tiny.py; csrc/tiny_model.hip) are in this library
     name = "hip"
@@ -159,6 +202,21 @@ class HipBackend:
         torch.cuda.synchronize()
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
+    def _call(self, label, symbol, dev, *args):
+        """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
+        a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
+        `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
+        collection, operands on the current device -- adds nothing around the call."""
+        fn = getattr(self.lib, symbol)
+        index = dev.index
+        if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
+            rc = fn(*args, _raw_stream(index) if _raw_stream is not None else _stream(dev))
+        else:
+            with _Timed(self, label, dev):
+                rc = fn(*args, _stream(dev))
+        if rc != 0:
+            _lib.check(rc, symbol)
+
     # ---- a1 --------------------------------------------------------------------------------
     def simple_reduce(self, q, k, v):
         dev = _require_device(q, k, v)
@@ -170,11 +228,9 @@ class HipBackend:
         v, ldv = _row_major(v, H * D)
         reduced = torch.empty(self.lib.dif_simple_reduced_len(H, M, D), dtype=torch.float32, device=dev)
         ws_bytes = self.lib.dif_simple_workspace_bytes(n, H, M, D)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        fn = getattr(self.lib, "dif_simple_reduce_" + sfx)
-        with _timed(self, "dif_simple_reduce_f32", dev):
-            rc = fn(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, n, H, M, D, _ptr(reduced), _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_simple_reduce_" + sfx)
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_simple_reduce_f32", "dif_simple_reduce_" + sfx, dev, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv,
+                   n, H, M, D, _ptr(reduced), _ptr(ws), ws_bytes)
         return reduced
 
     def project_reduce(self, x, Wq, bq, Wk, bk, Wv, bv, H, D):
@@ -183,17 +239,14 @@ class HipBackend:
         n, C = x.shape
         dt, sfx = _storage(x, Wq, bq, Wk, bk, Wv, bv)
         x, ldx = _row_major(x, C)
-        ws_ = [t.contiguous() for t in (Wq, bq, Wk, bk, Wv, bv)]
+        ws_ = _contig(Wq, bq, Wk, bk, Wv, bv)
         q = torch.empty((n, H, D), dtype=dt, device=dev)
         v = torch.empty((n, H, D), dtype=dt, device=dev)
         reduced = torch.empty(self.lib.dif_simple_reduced_len(H, D, D), dtype=torch.float32, device=dev)
         ws_bytes = self.lib.dif_project_reduce_workspace_bytes(n, H, D)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        fn = getattr(self.lib, "dif_project_reduce_" + sfx)
-        with _timed(self, "dif_project_reduce_f32", dev):
-            rc = fn(_ptr(x), ldx, n, C, *[_ptr(t) for t in ws_], H, D, _ptr(q), H * D, _ptr(v), H * D, _ptr(reduced),
-                    _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_project_reduce_" + sfx)
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_project_reduce_f32", "dif_project_reduce_" + sfx, dev, _ptr(x), ldx, n, C,
+                   *[_ptr(t) for t in ws_], H, D, _ptr(q), H * D, _ptr(v), H * D, _ptr(reduced), _ptr(ws), ws_bytes)
         return q, v, reduced
 
     def simple_apply(self, q, reduced, n_global, D):
@@ -203,10 +256,8 @@ class HipBackend:
         _f32(reduced, "reduced")
         q, ldq = _row_major(q, H * M)
         out = torch.empty((n, H, D), dtype=dt, device=dev)
-        fn = getattr(self.lib, "dif_simple_apply_" + sfx)
-        with _timed(self, "dif_simple_apply_f32", dev):
-            rc = fn(_ptr(q), ldq, _ptr(reduced), n, int(n_global), H, M, D, _ptr(out), H * D, _stream(dev))
-        _lib.check(rc, "dif_simple_apply_" + sfx)
+        self._call("dif_simple_apply_f32", "dif_simple_apply_" + sfx, dev, _ptr(q), ldq, _ptr(reduced), n,
+                   int(n_global), H, M, D, _ptr(out), H * D)
         return out
 
     # ---- a1 backward ------------------------------------------------------------------------
@@ -219,8 +270,7 @@ class HipBackend:
         sharded = shard is not None and shard.world > 1
         n_global = shard.n_global if sharded else n
         D = v.shape[2]
-        for t_, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (g, "grad")):
-            _f32(t_, nm)
+        _all_f32(q=q, k=k, v=v, out=out, grad=g)
         # q, k, v are usually column slices of one fused projection [n, 3 H D]: every kernel below takes a leading
         # dimension, so they go in as they are (three 34-MB copies per layer at C4 otherwise)
         (q, ldq), (k, ldk), (v, ldv) = _row_major(q, H * M), _row_major(k, H * M), _row_major(v, H * D)
@@ -229,12 +279,9 @@ class HipBackend:
         gn, gd = torch.empty((n, H, D), **f32), torch.empty((n, H), **f32)
         sums = torch.empty(H * M + 1, **f32)
         ws_bytes = self.lib.dif_simple_bwd_workspace_bytes(n, H, M, D)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_simple_bwd_prep_f32", dev):
-            rc = self.lib.dif_simple_bwd_prep_f32(_ptr(q), ldq, _ptr(g), H * D, _ptr(out), H * D, _ptr(reduced), n,
-                                                  int(n_global), H, M, D, _ptr(gn), _ptr(gd), _ptr(sums), _ptr(ws),
-                                                  ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_simple_bwd_prep_f32")
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_simple_bwd_prep_f32", "dif_simple_bwd_prep_f32", dev, _ptr(q), ldq, _ptr(g), H * D, _ptr(out),
+                   H * D, _ptr(reduced), n, int(n_global), H, M, D, _ptr(gn), _ptr(gd), _ptr(sums), _ptr(ws), ws_bytes)
         rec2 = self.simple_reduce(q, q, gn)                      # q^T gn, (sum q), sum gn
         if sharded:
             both = torch.cat([rec2, sums])
@@ -261,11 +308,9 @@ class HipBackend:
             ldg = None
 
         def rowgemm(A, K, mat, mat_t, bias, r, u, cin, beta, C, dst, lda=None, ldc=None):
-            with _timed(self, "dif_rowgemm_f32", dev):
-                rc_ = self.lib.dif_rowgemm_f32(_ptr(A), lda or H * K, _ptr(mat), D, M * D, mat_t, 1.0, _ptr(bias), _ptr(r), _ptr(u),
-                                               1.0, _ptr(cin), ldc or H * C, _ptr(beta), n, H, K, C, _ptr(dst), ldg or H * C,
-                                               _stream(dev))
-            _lib.check(rc_, "dif_rowgemm_f32")
+            self._call("dif_rowgemm_f32", "dif_rowgemm_f32", dev, _ptr(A), lda or H * K, _ptr(mat), D, M * D, mat_t, 1.0,
+                       _ptr(bias), _ptr(r), _ptr(u), 1.0, _ptr(cin), ldc or H * C, _ptr(beta), n, H, K, C, _ptr(dst),
+                       ldg or H * C)
 
         rowgemm(gn, D, ktv_s, 1, None, gd, ks_s, None, None, M, dq)   # dq_main = gn (s KtV)^T + gd (s ks)
         # T = s * dL/ds = sum q . dq_main.  (Algebraically also -(vs . dvs) - N sum gd, but those two terms cancel to
@@ -291,20 +336,14 @@ class HipBackend:
         v, ldv = _row_major(v, H * D)
         out = torch.empty((N, H, D), dtype=dt, device=dev)
         ws_bytes = self.lib.dif_sigmoid_workspace_bytes(N, L, H, M, D)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        if want_den:
+        ws = _workspace(ws_bytes, dev, or_none=True)
+        head = (_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, N, L, H, M, D, _ptr(out), H * D)
+        if want_den:                         # the _fwd_ symbol takes `den` between the output and the workspace
             _f32(q, "q")
             den = torch.empty((N, H), dtype=torch.float32, device=dev)
-            with _timed(self, "dif_sigmoid_attn_fwd_f32", dev):
-                rc = self.lib.dif_sigmoid_attn_fwd_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, N, L, H, M, D, _ptr(out),
-                                                       H * D, _ptr(den), _ptr(ws), ws_bytes, _stream(dev))
-            _lib.check(rc, "dif_sigmoid_attn_fwd_f32")
+            self._call("dif_sigmoid_attn_fwd_f32", "dif_sigmoid_attn_fwd_f32", dev, *head, _ptr(den), _ptr(ws), ws_bytes)
             return out, den
-        name = "dif_sigmoid_attn_" + sfx
-        with _timed(self, name, dev):
-            rc = getattr(self.lib, name)(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, N, L, H, M, D, _ptr(out), H * D, _ptr(ws),
-                                         ws_bytes, _stream(dev))
-        _lib.check(rc, name)
+        self._call("dif_sigmoid_attn_" + sfx, "dif_sigmoid_attn_" + sfx, dev, *head, _ptr(ws), ws_bytes)
         return out
 
     def sigmoid_backward(self, q, k, v, out, den, g):
@@ -314,8 +353,7 @@ class HipBackend:
         dev = _require_device(q, k, v, out, den, g)
         N, H, M = q.shape
         L, D = k.shape[0], v.shape[2]
-        for t_, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (den, "den"), (g, "grad")):
-            _f32(t_, nm)
+        _all_f32(q=q, k=k, v=v, out=out, den=den, grad=g)
         q, ldq = _row_major(q, H * M)
         k, ldk = _row_major(k, H * M)
         v, ldv = _row_major(v, H * D)
@@ -324,12 +362,10 @@ class HipBackend:
         f32 = dict(dtype=torch.float32, device=dev)
         dq, dk, dv = torch.empty((N, H, M), **f32), torch.empty((L, H, M), **f32), torch.empty((L, H, D), **f32)
         ws_bytes = self.lib.dif_sigmoid_bwd_workspace_bytes(N, L, H, M, D)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_sigmoid_attn_bwd_f32", dev):
-            rc = self.lib.dif_sigmoid_attn_bwd_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(out), H * D, _ptr(den),
-                                                   _ptr(g), ldg, N, L, H, M, D, _ptr(dq), H * M, _ptr(dk), H * M, _ptr(dv),
-                                                   H * D, _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_sigmoid_attn_bwd_f32")
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_sigmoid_attn_bwd_f32", "dif_sigmoid_attn_bwd_f32", dev, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv,
+                   _ptr(out), H * D, _ptr(den), _ptr(g), ldg, N, L, H, M, D, _ptr(dq), H * M, _ptr(dk), H * M, _ptr(dv),
+                   H * D, _ptr(ws), ws_bytes)
         return dq, dk, dv
 
     # ---- f4: batch of graphs (physical particle/difformer-v2.py:71-137) ---------------------
@@ -339,8 +375,7 @@ class HipBackend:
         dev = _require_device(q, k, v, graph_ptr)
         N, H, M = q.shape
         D = v.shape[2]
-        for t_, nm in ((q, "q"), (k, "k"), (v, "v")):
-            _f32(t_, nm)
+        _all_f32(q=q, k=k, v=v)
         if graph_ptr.dtype != torch.int32 or not graph_ptr.is_contiguous():
             raise TypeError("difformer_amd: graph_ptr must be a contiguous int32 tensor [B+1]")
         q, ldq = _row_major(q, H * M)
@@ -348,20 +383,15 @@ class HipBackend:
         v, ldv = _row_major(v, H * D)
         out = torch.empty((N, H, D), dtype=torch.float32, device=dev)
         ws_bytes = self.lib.dif_batched_simple_workspace_bytes()
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        if want_den:
+        ws = _workspace(ws_bytes, dev)
+        head = (_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(graph_ptr), graph_ptr.numel() - 1, N, H, M, D, _ptr(out),
+                H * D)
+        if want_den:                         # the _fwd_ symbol takes `den` between the output and the workspace
             den = torch.empty((N, H), dtype=torch.float32, device=dev)
-            with _timed(self, "dif_batched_simple_attn_fwd_f32", dev):
-                rc = self.lib.dif_batched_simple_attn_fwd_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(graph_ptr),
-                                                              graph_ptr.numel() - 1, N, H, M, D, _ptr(out), H * D, _ptr(den),
-                                                              _ptr(ws), ws_bytes, _stream(dev))
-            _lib.check(rc, "dif_batched_simple_attn_fwd_f32")
+            self._call("dif_batched_simple_attn_fwd_f32", "dif_batched_simple_attn_fwd_f32", dev, *head, _ptr(den),
+                       _ptr(ws), ws_bytes)
             return out, den, ws.view(torch.float32)[-2:].clone()
-        with _timed(self, "dif_batched_simple_attn_f32", dev):
-            rc = self.lib.dif_batched_simple_attn_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(graph_ptr),
-                                                      graph_ptr.numel() - 1, N, H, M, D, _ptr(out), H * D, _ptr(ws),
-                                                      ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_batched_simple_attn_f32")
+        self._call("dif_batched_simple_attn_f32", "dif_batched_simple_attn_f32", dev, *head, _ptr(ws), ws_bytes)
         return out
 
     def batched_simple_backward(self, q, k, v, out, den, sumsq, g, graph_ptr):
@@ -371,9 +401,8 @@ class HipBackend:
         dev = _require_device(q, k, v, out, den, sumsq, g, graph_ptr)
         N, H, M = q.shape
         D = v.shape[2]
-        for t_, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (den, "den"), (g, "grad")):
-            _f32(t_, nm)
-        q, k, v, g = (t_.contiguous() for t_ in (q, k, v, g))
+        _all_f32(q=q, k=k, v=v, out=out, den=den, grad=g)
+        q, k, v, g = _contig(q, k, v, g)
         gn = (g / den.unsqueeze(-1)).contiguous()
         gd = (-(g * out).sum(dim=-1) / den).contiguous()
         B = graph_ptr.numel() - 1
@@ -381,11 +410,9 @@ class HipBackend:
         def raw(a, b, c, rs, vw, vs_is_s):
             Ma, Dc = a.shape[2], c.shape[2]
             dst = torch.empty((N, H, Dc), dtype=torch.float32, device=dev)
-            with _timed(self, "dif_batched_simple_raw_f32", dev):
-                rc = self.lib.dif_batched_simple_raw_f32(_ptr(a), H * Ma, _ptr(b), H * Ma, _ptr(c), H * Dc, _ptr(graph_ptr), B, N,
-                                                         H, Ma, Dc, _ptr(sumsq), _ptr(rs), _ptr(vw), int(vs_is_s), _ptr(dst),
-                                                         H * Dc, _stream(dev))
-            _lib.check(rc, "dif_batched_simple_raw_f32")
+            self._call("dif_batched_simple_raw_f32", "dif_batched_simple_raw_f32", dev, _ptr(a), H * Ma, _ptr(b), H * Ma,
+                       _ptr(c), H * Dc, _ptr(graph_ptr), B, N, H, Ma, Dc, _ptr(sumsq), _ptr(rs), _ptr(vw), int(vs_is_s),
+                       _ptr(dst), H * Dc)
             return dst
 
         dq = raw(gn, v, k, gd, None, 1)                 # s gn (sum v (x) k) + s gd ksum_b
@@ -402,8 +429,7 @@ class HipBackend:
         dev = _require_device(q, k, v, ranked_first, pos_count)
         N, H, M = q.shape
         D = v.shape[2]
-        for t_, nm in ((q, "q"), (k, "k"), (v, "v")):
-            _f32(t_, nm)
+        _all_f32(q=q, k=k, v=v)
         for t_ in (ranked_first, pos_count):
             if t_.dtype != torch.int32 or not t_.is_contiguous():
                 raise TypeError("difformer_amd: ranked_first / pos_count must be contiguous int32 tensors")
@@ -411,19 +437,13 @@ class HipBackend:
         k, ldk = _row_major(k, H * M)
         v, ldv = _row_major(v, H * D)
         out = torch.empty((N, H, D), dtype=torch.float32, device=dev)
-        if want_den:
+        args = (_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(ranked_first), _ptr(pos_count), ranked_first.numel(),
+                pos_count.numel(), H, M, D, _ptr(out), H * D)
+        if want_den:                         # the _fwd_ symbol takes `den` after the output
             den = torch.empty((N, H), dtype=torch.float32, device=dev)
-            with _timed(self, "dif_batched_sigmoid_attn_fwd_f32", dev):
-                rc = self.lib.dif_batched_sigmoid_attn_fwd_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(ranked_first),
-                                                               _ptr(pos_count), ranked_first.numel(), pos_count.numel(), H, M,
-                                                               D, _ptr(out), H * D, _ptr(den), _stream(dev))
-            _lib.check(rc, "dif_batched_sigmoid_attn_fwd_f32")
+            self._call("dif_batched_sigmoid_attn_fwd_f32", "dif_batched_sigmoid_attn_fwd_f32", dev, *args, _ptr(den))
             return out, den
-        with _timed(self, "dif_batched_sigmoid_attn_f32", dev):
-            rc = self.lib.dif_batched_sigmoid_attn_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(ranked_first),
-                                                       _ptr(pos_count), ranked_first.numel(), pos_count.numel(), H, M, D,
-                                                       _ptr(out), H * D, _stream(dev))
-        _lib.check(rc, "dif_batched_sigmoid_attn_f32")
+        self._call("dif_batched_sigmoid_attn_f32", "dif_batched_sigmoid_attn_f32", dev, *args)
         return out
 
     def batched_sigmoid_backward(self, q, k, v, out, den, g, ranked_first, pos_count):
@@ -432,8 +452,7 @@ class HipBackend:
         dev = _require_device(q, k, v, out, den, g, ranked_first, pos_count)
         N, H, M = q.shape
         D = v.shape[2]
-        for t_, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (den, "den"), (g, "grad")):
-            _f32(t_, nm)
+        _all_f32(q=q, k=k, v=v, out=out, den=den, grad=g)
         q, ldq = _row_major(q, H * M)
         k, ldk = _row_major(k, H * M)
         v, ldv = _row_major(v, H * D)
@@ -441,20 +460,17 @@ class HipBackend:
         f32 = dict(dtype=torch.float32, device=dev)
         dq, dk, dv = torch.empty((N, H, M), **f32), torch.empty((N, H, M), **f32), torch.empty((N, H, D), **f32)
         ws_bytes = self.lib.dif_batched_sigmoid_bwd_workspace_bytes(N, H)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_batched_sigmoid_attn_bwd_f32", dev):
-            rc = self.lib.dif_batched_sigmoid_attn_bwd_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(out), H * D, _ptr(den),
-                                                           _ptr(g), H * D, _ptr(ranked_first), _ptr(pos_count),
-                                                           ranked_first.numel(), pos_count.numel(), N, H, M, D, _ptr(dq), H * M,
-                                                           _ptr(dk), H * M, _ptr(dv), H * D, _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_batched_sigmoid_attn_bwd_f32")
+        ws = _workspace(ws_bytes, dev, floor=16)
+        self._call("dif_batched_sigmoid_attn_bwd_f32", "dif_batched_sigmoid_attn_bwd_f32", dev, _ptr(q), ldq, _ptr(k), ldk,
+                   _ptr(v), ldv, _ptr(out), H * D, _ptr(den), _ptr(g), H * D, _ptr(ranked_first), _ptr(pos_count),
+                   ranked_first.numel(), pos_count.numel(), N, H, M, D, _ptr(dq), H * M, _ptr(dk), H * M, _ptr(dv), H * D,
+                   _ptr(ws), ws_bytes)
         return dq, dk, dv
 
     # ---- a3 --------------------------------------------------------------------------------
     def csr_build(self, edge_index, edge_weight, num_nodes, n_blocks=1, transpose=False, block_rows=0):
         dev = _require_device(edge_index, edge_weight)
-        if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
-            raise TypeError("difformer_amd: edge_index must be an int64 tensor of shape [2, E]")
+        _check_edge_index(edge_index)
         ei = edge_index.contiguous()
         E = int(ei.shape[1])
         ew = None
@@ -470,12 +486,9 @@ class HipBackend:
         if n_blocks > 1:
             blkptr = torch.empty((n_blocks + 1) * num_nodes, dtype=torch.int32, device=dev)
         ws_bytes = self.lib.dif_csr_workspace_bytes(E, num_nodes, n_blocks)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_csr_build", dev):
-            rc = self.lib.dif_csr_build(_ptr(ei), E, num_nodes, _ptr(ew), n_blocks, int(block_rows), int(bool(transpose)), _ptr(rowptr),
-                                        _ptr(blkptr),
-                                        _ptr(src), _ptr(val), _ptr(status), _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_csr_build")
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_csr_build", "dif_csr_build", dev, _ptr(ei), E, num_nodes, _ptr(ew), n_blocks, int(block_rows),
+                   int(bool(transpose)), _ptr(rowptr), _ptr(blkptr), _ptr(src), _ptr(val), _ptr(status), _ptr(ws), ws_bytes)
         bad, longest = status.tolist()  # one sync per (cold) build; the longest row rides along (kernel selection)
         if bad != 0:
             raise IndexError(f"difformer_amd: edge_index holds node ids outside [0, {num_nodes})")
@@ -497,43 +510,30 @@ class HipBackend:
                     None if ew is None else torch.empty(0, dtype=torch.float32, device=dev))
         out_ei = torch.empty((2, max(E, 1)), dtype=torch.int64, device=dev)
         out_w = None if ew is None else torch.empty(max(E, 1), dtype=torch.float32, device=dev)
-        res = torch.zeros(2, dtype=torch.int64, device=dev)    # [kept count | status word]: ONE read-back
-        count, status = res[:1], res[1:].view(torch.int32)
+        res, count, status = _kept_status(dev)
         ws_bytes = self.lib.dif_subgraph_workspace_bytes(E, num_nodes)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_subgraph", dev):
-            rc = self.lib.dif_subgraph(_ptr(ei), E, num_nodes, _ptr(sub), B, _ptr(ew), _ptr(out_ei), _ptr(out_w),
-                                       _ptr(count), _ptr(status), _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_subgraph")
-        kept, bad = res.tolist()                                # one sync: the result size is data dependent
-        bad &= 0xFFFFFFFF
-        if bad:
-            raise IndexError(f"difformer_amd: subset / edge_index hold node ids outside [0, {num_nodes})")
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_subgraph", "dif_subgraph", dev, _ptr(ei), E, num_nodes, _ptr(sub), B, _ptr(ew), _ptr(out_ei),
+                   _ptr(out_w), _ptr(count), _ptr(status), _ptr(ws), ws_bytes)
+        kept = _read_kept(res, "subset / edge_index hold", num_nodes)
         out = torch.stack([out_ei[0, :kept], out_ei[1, :kept]])
         return out, (None if out_w is None else out_w[:kept].clone())
 
     def graph_prepare(self, edge_index, num_nodes, undirected=False, remove_loops=False, add_loops=False):
         """to_undirected -> remove_self_loops -> add_self_loops (any subset, in that order) on the device -> [2, E']."""
         dev = _require_device(edge_index)
-        if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
-            raise TypeError("difformer_amd: edge_index must be an int64 tensor of shape [2, E]")
+        _check_edge_index(edge_index)
         ei = edge_index.contiguous()
         E = int(ei.shape[1])
         cap = (2 * E if undirected else E) + (num_nodes if add_loops else 0)
         out = torch.empty((2, max(cap, 1)), dtype=torch.int64, device=dev)
-        res = torch.zeros(2, dtype=torch.int64, device=dev)    # [kept count | status word]: ONE read-back
-        count, status = res[:1], res[1:].view(torch.int32)
+        res, count, status = _kept_status(dev)
         ws_bytes = self.lib.dif_graph_prepare_workspace_bytes(E, num_nodes, int(bool(undirected)))
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_graph_prepare", dev):
-            rc = self.lib.dif_graph_prepare(_ptr(ei), E, num_nodes, int(bool(undirected)), int(bool(remove_loops)),
-                                            int(bool(add_loops)), max(cap, 1), _ptr(out), _ptr(count), _ptr(status), _ptr(ws),
-                                            ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_graph_prepare")
-        kept, bad = res.tolist()                                # one sync: the result size is data dependent
-        bad &= 0xFFFFFFFF
-        if bad:
-            raise IndexError(f"difformer_amd: edge_index holds node ids outside [0, {num_nodes})")
+        ws = _workspace(ws_bytes, dev, floor=256)
+        self._call("dif_graph_prepare", "dif_graph_prepare", dev, _ptr(ei), E, num_nodes, int(bool(undirected)),
+                   int(bool(remove_loops)), int(bool(add_loops)), max(cap, 1), _ptr(out), _ptr(count), _ptr(status),
+                   _ptr(ws), ws_bytes)
+        kept = _read_kept(res, "edge_index holds", num_nodes)
         return torch.stack([out[0, :kept], out[1, :kept]])
 
     def subgraph_batches(self, perm, batch_size, edge_index, edge_weight, num_nodes, build_csr=False):
@@ -551,11 +551,9 @@ class HipBackend:
         bptr = torch.empty(nb + 1, dtype=torch.int64, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
         ws_bytes = self.lib.dif_subgraph_batches_workspace_bytes(E, num_nodes, nb)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_subgraph_batches", dev):
-            rc = self.lib.dif_subgraph_batches_group(_ptr(ei), E, num_nodes, _ptr(pm), M, int(batch_size), _ptr(bptr),
-                                                     _ptr(status), _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_subgraph_batches_group")
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_subgraph_batches", "dif_subgraph_batches_group", dev, _ptr(ei), E, num_nodes, _ptr(pm), M,
+                   int(batch_size), _ptr(bptr), _ptr(status), _ptr(ws), ws_bytes)
         ptr = bptr.tolist()                                   # one sync per epoch: the result size is data dependent
         bad = int(status.item())
         if bad & 1:
@@ -565,43 +563,35 @@ class HipBackend:
         kept = ptr[-1]
         out_ei = torch.empty((2, max(kept, 1)), dtype=torch.int64, device=dev)
         out_w = None if ew is None else torch.empty(max(kept, 1), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_subgraph_batches", dev):
-            rc = self.lib.dif_subgraph_batches_emit(_ptr(ei), E, num_nodes, M, int(batch_size), _ptr(ew), _ptr(bptr), kept,
-                                                    _ptr(out_ei), _ptr(out_w), _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_subgraph_batches_emit")
+        self._call("dif_subgraph_batches", "dif_subgraph_batches_emit", dev, _ptr(ei), E, num_nodes, M, int(batch_size),
+                   _ptr(ew), _ptr(bptr), kept, _ptr(out_ei), _ptr(out_w), _ptr(ws), ws_bytes)
         csr = None
         if build_csr:
             rowptr = torch.empty(M + 1, dtype=torch.int32, device=dev)
             src = torch.empty(max(kept, 1), dtype=torch.int32, device=dev)
             val = torch.empty(max(kept, 1), dtype=torch.float32, device=dev)
             ws2_bytes = self.lib.dif_subgraph_batches_csr_workspace_bytes(kept, M)
-            ws2 = torch.empty(ws2_bytes, dtype=torch.uint8, device=dev)
-            with _timed(self, "dif_subgraph_batches", dev):
-                rc = self.lib.dif_subgraph_batches_csr(_ptr(ei), E, num_nodes, M, int(batch_size), _ptr(ew), kept, _ptr(ws),
-                                                       ws_bytes, _ptr(rowptr), _ptr(src), _ptr(val), _ptr(ws2), ws2_bytes,
-                                                       _stream(dev))
-            _lib.check(rc, "dif_subgraph_batches_csr")
+            ws2 = _workspace(ws2_bytes, dev)
+            self._call("dif_subgraph_batches", "dif_subgraph_batches_csr", dev, _ptr(ei), E, num_nodes, M, int(batch_size),
+                       _ptr(ew), kept, _ptr(ws), ws_bytes, _ptr(rowptr), _ptr(src), _ptr(val), _ptr(ws2), ws2_bytes)
             csr = (rowptr, src, val)
         return out_ei[:, :kept], (None if out_w is None else out_w[:kept]), ptr, csr
 
     def edge_weight_grad(self, edge_index, edge_weight, rowptr, n_nodes, g, x, scale=1.0):
         """d loss / d edge_weight of the aggregation (difformer.py:73 under autograd): g, x [n_nodes, F] -> [E]."""
         dev = _require_device(edge_index, edge_weight, rowptr, g, x)
-        if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
-            raise TypeError("difformer_amd: edge_index must be int64 [2, E]")
+        _check_edge_index(edge_index)
         E, F = edge_index.shape[1], x.shape[1]
         if g.shape != x.shape or x.shape[0] != n_nodes:
             raise ValueError(f"difformer_amd: edge_weight_grad needs g and x as [{n_nodes}, F] (got {tuple(g.shape)}, {tuple(x.shape)})")
-        _f32(g, "g"), _f32(x, "x")
+        _all_f32(g=g, x=x)
         w = _f32(edge_weight, "edge_weight").detach().contiguous()
         ei = edge_index.contiguous()
         g, ldg = _row_major(g, F)
         x, ldx = _row_major(x, F)
         dw = torch.empty(E, dtype=torch.float32, device=dev)
-        with _timed(self, "dif_gcn_edge_weight_grad_f32", dev):
-            rc = self.lib.dif_gcn_edge_weight_grad_f32(_ptr(ei), E, n_nodes, _ptr(w), _ptr(rowptr), _ptr(g), ldg, _ptr(x), ldx,
-                                                       F, float(scale), _ptr(dw), _stream(dev))
-        _lib.check(rc, "dif_gcn_edge_weight_grad_f32")
+        self._call("dif_gcn_edge_weight_grad_f32", "dif_gcn_edge_weight_grad_f32", dev, _ptr(ei), E, n_nodes, _ptr(w),
+                   _ptr(rowptr), _ptr(g), ldg, _ptr(x), ldx, F, float(scale), _ptr(dw))
         return dw
 
     def spmm(self, rowptr, blkptr, n_blocks, src, val, n_nodes, nnz, x, row_begin, n_rows, attn=None, attn_scale=1.0,
@@ -627,15 +617,10 @@ class HipBackend:
         phase, own_lo, own_hi, scratch, x_row0 = part if part is not None else (None, 0, 0, None, 0)
         if phase != 0 and x.shape[0] != n_nodes:
             raise ValueError(f"difformer_amd: spmm needs all {n_nodes} source rows, got {x.shape[0]}")
-        lda = ldx0 = ldp = 0
-        if attn is not None:
-            attn, lda = _row_major(attn, F)
-        if x0 is not None:
-            x0, ldx0 = _row_major(x0, F)
-        if prev is not None:
-            prev, ldp = _row_major(prev, F)
-        if lw is not None:
-            lw, lb = lw.contiguous(), lb.contiguous()
+        attn, lda = _rows(attn, F)
+        x0, ldx0 = _rows(x0, F)
+        prev, ldp = _rows(prev, F)
+        lw, lb = _contig(lw, lb)
         out = torch.empty((n_rows, F), dtype=dt, device=dev)
         head = (_ptr(rowptr), _ptr(blkptr), n_blocks, _ptr(src), _ptr(val), n_nodes, nnz, _ptr(x), ldx, row_begin, n_rows, F,
                 _ptr(attn), lda, float(attn_scale), float(gcn_scale), _ptr(order), int(n_split))
@@ -644,28 +629,22 @@ class HipBackend:
         if part is not None:
             sbytes = self.lib.dif_gcn_spmm_part_scratch_bytes(n_rows, int(n_split), F)
             if scratch is None:
-                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+                scratch = _workspace(sbytes, dev)
             # part 0 indexes x by GLOBAL source row but only ever touches this rank's own rows: hand it the pointer
             # the first own row would have inside a full [n_nodes, F] array
             xp = ctypes.c_void_p(x.data_ptr() - int(x_row0) * ldx * x.element_size())
             head = head[:7] + (xp,) + head[8:]
-            fn = self.lib.dif_gcn_spmm_part_bf16 if sfx == "bf16" else self.lib.dif_gcn_spmm_part_f32
-            with _timed(self, "dif_gcn_spmm_f32", dev):
-                rc = fn(*head, int(tail is not None), *tail_args, int(phase), int(own_lo), int(own_hi),
-                        PART0_WORKGROUPS if phase == 0 else 0, _ptr(scratch), sbytes, _ptr(out), F, _stream(dev))
-            _lib.check(rc, "dif_gcn_spmm_part")
+            self._call("dif_gcn_spmm_f32", "dif_gcn_spmm_part_" + sfx, dev, *head, int(tail is not None), *tail_args,
+                       int(phase), int(own_lo), int(own_hi), PART0_WORKGROUPS if phase == 0 else 0, _ptr(scratch), sbytes,
+                       _ptr(out), F)
             return scratch if phase == 0 else out
-        with _timed(self, "dif_gcn_spmm_f32", dev):
-            if sfx == "bf16":
-                name = "dif_gcn_spmm_tail_bf16"
-                rc = self.lib.dif_gcn_spmm_tail_bf16(*head, int(tail is not None), *tail_args, _ptr(out), F, _stream(dev))
-            elif tail is None:
-                name = "dif_gcn_spmm_f32"
-                rc = self.lib.dif_gcn_spmm_f32(*head, _ptr(out), F, _stream(dev))
-            else:
-                name = "dif_gcn_spmm_tail_f32"
-                rc = self.lib.dif_gcn_spmm_tail_f32(*head, *tail_args, _ptr(out), F, _stream(dev))
-        _lib.check(rc, name)
+        if sfx == "bf16":
+            symbol, args = "dif_gcn_spmm_tail_bf16", head + (int(tail is not None),) + tail_args
+        elif tail is None:
+            symbol, args = "dif_gcn_spmm_f32", head
+        else:
+            symbol, args = "dif_gcn_spmm_tail_f32", head + tail_args
+        self._call("dif_gcn_spmm_f32", symbol, dev, *args, _ptr(out), F)
         return out
 
     # ---- a1 + a4 + tail in closed form (csrc/simple_layer.hip) ---------------------------------------------------------
@@ -675,62 +654,45 @@ class HipBackend:
         dev = _require_device(x, rowptr)
         dt, sfx = _storage(x)
         n, C = x.shape
-        x, ldx = _row_major(x, C)
-        if ldx % 4 or x.data_ptr() % (4 * x.element_size()):
-            x, ldx = x.contiguous(), C
+        x, ldx = _rows(x, C, align=True)
         record = torch.empty(C * C + C + 2, dtype=torch.float32, device=dev)
         ws_bytes = self.lib.dif_gram_workspace_bytes(n, C)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        ws = _workspace(ws_bytes, dev, floor=16)
         if sfx == "bf16":        # bfloat16 rows, float32 record; no slice-major copy (the sliced product is float32-only)
             if plan is not None:
                 raise TypeError("difformer_amd: the slice-major copy of the sliced product is float32-only")
-            with _timed(self, "dif_gram_f32", dev):
-                rc = self.lib.dif_gram_bf16(_ptr(x), ldx, n, C, _ptr(record), _ptr(ws), ws_bytes, _stream(dev))
-            _lib.check(rc, "dif_gram_bf16")
+            self._call("dif_gram_f32", "dif_gram_bf16", dev, _ptr(x), ldx, n, C, _ptr(record), _ptr(ws), ws_bytes)
             return record, None
-        ys = None
-        if plan is not None:
-            ys = torch.empty((C // 4, int(plan[6]) * int(plan[7]), 4), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_gram_f32", dev):
-            rc = self.lib.dif_gram_f32(_ptr(x), ldx, n, C, _ptr(rowptr) if plan is not None else None, plan, _ptr(ys),
-                                       _ptr(record), _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_gram_f32")
+        ys = None if plan is None else _slice_major(C, plan, dev)
+        self._call("dif_gram_f32", "dif_gram_f32", dev, _ptr(x), ldx, n, C, _ptr(rowptr) if plan is not None else None,
+                   plan, _ptr(ys), _ptr(record), _ptr(ws), ws_bytes)
         return record, ys
 
     def input_gram(self, x, weight, bias, ln_weight, ln_bias, eps, relu, rowptr=None, plan=None):
         """Input layer + the first closed-form layer's products in one pass (csrc/simple_layer.hip, input_gram_kernel):
         x [n, C_in <= 64] fp32 -> (h = ReLU(LayerNorm(x W^T + b)) [n, D], record of h as `gram` leaves it, ys | None)."""
         dev = _require_device(x, weight, bias, ln_weight, ln_bias, rowptr)
-        for t, name in ((x, "x"), (weight, "weight"), (bias, "bias")):
-            _f32(t, name)
+        _all_f32(x=x, weight=weight, bias=bias)
         n, C = x.shape
         D = weight.shape[0]
         x, ldx = _row_major(x, C)
-        weight, bias = weight.contiguous(), bias.contiguous()
-        if ln_weight is not None:
-            ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
+        weight, bias, ln_weight, ln_bias = _contig(weight, bias, ln_weight, ln_bias)
         out = torch.empty((n, D), dtype=torch.float32, device=dev)
         record = torch.empty(D * D + D + 2, dtype=torch.float32, device=dev)
         ws_bytes = self.lib.dif_gram_workspace_bytes(n, D)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        ys = None
-        if plan is not None:
-            ys = torch.empty((D // 4, int(plan[6]) * int(plan[7]), 4), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_input_gram_f32", dev):
-            rc = self.lib.dif_input_gram_f32(_ptr(x), ldx, n, C, _ptr(weight), _ptr(bias), D, _ptr(ln_weight), _ptr(ln_bias),
-                                             float(eps), int(bool(relu)), _ptr(out), D, _ptr(rowptr) if plan is not None else None,
-                                             plan, _ptr(ys), _ptr(record), _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_input_gram_f32")
+        ws = _workspace(ws_bytes, dev, floor=16)
+        ys = None if plan is None else _slice_major(D, plan, dev)
+        self._call("dif_input_gram_f32", "dif_input_gram_f32", dev, _ptr(x), ldx, n, C, _ptr(weight), _ptr(bias), D,
+                   _ptr(ln_weight), _ptr(ln_bias), float(eps), int(bool(relu)), _ptr(out), D,
+                   _ptr(rowptr) if plan is not None else None, plan, _ptr(ys), _ptr(record), _ptr(ws), ws_bytes)
         return out, record, ys
 
     def simple_coeffs(self, record, n_global, C, D, Wq, bq, Wk, bk, Wv, bv, attn_scale):
         dev = _require_device(record, Wq, bq, Wk, bk, Wv, bv)
-        ws_ = [None if t is None else _f32(t, "weight").contiguous() for t in (Wq, bq, Wk, bk, Wv, bv)]
+        ws_ = _contig(Wq, bq, Wk, bk, Wv, bv, f32="weight")
         coef = torch.empty(self.lib.dif_simple_coeffs_len(C, D), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_simple_coeffs_f32", dev):
-            rc = self.lib.dif_simple_coeffs_f32(_ptr(record), int(n_global), C, D, *[_ptr(t) for t in ws_], float(attn_scale),
-                                                _ptr(coef), _stream(dev))
-        _lib.check(rc, "dif_simple_coeffs_f32")
+        self._call("dif_simple_coeffs_f32", "dif_simple_coeffs_f32", dev, _ptr(record), int(n_global), C, D,
+                   *[_ptr(t) for t in ws_], float(attn_scale), _ptr(coef))
         return coef
 
     def gram_coeffs(self, x, n_global, C, D, Wq, bq, Wk, bk, Wv, bv, attn_scale):
@@ -739,18 +701,14 @@ class HipBackend:
         dev = _require_device(x, Wq, bq, Wk, bk, Wv, bv)
         _f32(x, "x")
         n = x.shape[0]
-        x, ldx = _row_major(x, C)
-        if ldx % 4 or x.data_ptr() % 16:
-            x, ldx = x.contiguous(), C
-        ws_ = [None if t is None else _f32(t, "weight").contiguous() for t in (Wq, bq, Wk, bk, Wv, bv)]
+        x, ldx = _rows(x, C, align=True)
+        ws_ = _contig(Wq, bq, Wk, bk, Wv, bv, f32="weight")
         record = torch.empty(C * C + C + 2, dtype=torch.float32, device=dev)
         coef = torch.empty(self.lib.dif_simple_coeffs_len(C, D), dtype=torch.float32, device=dev)
         ws_bytes = self.lib.dif_gram_workspace_bytes(n, C)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_gram_coeffs_f32", dev):
-            rc = self.lib.dif_gram_coeffs_f32(_ptr(x), ldx, n, C, D, *[_ptr(t) for t in ws_], int(n_global), float(attn_scale),
-                                              _ptr(coef), _ptr(record), _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_gram_coeffs_f32")
+        ws = _workspace(ws_bytes, dev, floor=16)
+        self._call("dif_gram_coeffs_f32", "dif_gram_coeffs_f32", dev, _ptr(x), ldx, n, C, D, *[_ptr(t) for t in ws_],
+                   int(n_global), float(attn_scale), _ptr(coef), _ptr(record), _ptr(ws), ws_bytes)
         return record, coef
 
     def row_gemm(self, A, mat, bias=None, accumulate=None):
@@ -762,20 +720,16 @@ class HipBackend:
         if K > 512 or any(t_ is not None and t_.dtype != torch.float32 for t_ in (A, mat, bias, accumulate)):
             return None
         A, lda = _row_major(A, K)
-        mat = mat.contiguous()
-        ldc = 0
+        mat, bias = _contig(mat, bias)
+        accumulate, ldc = _rows(accumulate, C)
         one = None
         if accumulate is not None:
-            accumulate, ldc = _row_major(accumulate, C)
             one = self._ones.get(dev)
             if one is None:
                 one = self._ones[dev] = torch.ones(1, dtype=torch.float32, device=dev)
         out = torch.empty((n, C), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_rowgemm_f32", dev):
-            rc = self.lib.dif_rowgemm_f32(_ptr(A), lda, _ptr(mat), C, 0, 0, 1.0, _ptr(None if bias is None else bias.contiguous()),
-                                          None, None, 1.0, _ptr(accumulate), ldc, _ptr(one), n, 1, K, C, _ptr(out), C,
-                                          _stream(dev))
-        _lib.check(rc, "dif_rowgemm_f32")
+        self._call("dif_rowgemm_f32", "dif_rowgemm_f32", dev, _ptr(A), lda, _ptr(mat), C, 0, 0, 1.0, _ptr(bias), None, None,
+                   1.0, _ptr(accumulate), ldc, _ptr(one), n, 1, K, C, _ptr(out), C)
         return out
 
     def closed_form_attn_backward(self, x, coef, D, d, dx_in=None, row_sums=None):
@@ -788,9 +742,7 @@ class HipBackend:
             return None
         x, ldx = _row_major(x, C)
         d, ldd = _row_major(d, D)
-        ldi = 0
-        if dx_in is not None:
-            dx_in, ldi = _row_major(dx_in, C)
+        dx_in, ldi = _rows(dx_in, C)
         if any(ld % 4 for ld in (ldx, ldd, ldi)) or any(t_ is not None and t_.data_ptr() % 16 for t_ in (x, d, dx_in)):
             return None
         d_num = torch.empty((n, D), dtype=torch.float32, device=dev)
@@ -799,11 +751,8 @@ class HipBackend:
         if row_sums is not None:
             row_sums = _f32(row_sums, "row_sums").contiguous()
         parts = torch.empty((self.lib.dif_closed_form_attn_bwd_groups(n), 132), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_simple_layer_f32", dev):
-            rc = self.lib.dif_closed_form_attn_bwd_f32(_ptr(x), ldx, n, C, D, _ptr(coef), _ptr(d), ldd, _ptr(dx_in), ldi,
-                                                       _ptr(d_num), _ptr(d_den), _ptr(dx), C, _ptr(row_sums), _ptr(parts),
-                                                       _stream(dev))
-        _lib.check(rc, "dif_closed_form_attn_bwd_f32")
+        self._call("dif_simple_layer_f32", "dif_closed_form_attn_bwd_f32", dev, _ptr(x), ldx, n, C, D, _ptr(coef), _ptr(d),
+                   ldd, _ptr(dx_in), ldi, _ptr(d_num), _ptr(d_den), _ptr(dx), C, _ptr(row_sums), _ptr(parts))
         sums = parts.sum(dim=0)                      # one partial record per workgroup, added in a fixed order
         return d_num, d_den, dx, sums[:C], sums[128], (sums[64: 64 + D] if row_sums is not None else None)
 
@@ -811,15 +760,13 @@ class HipBackend:
         """Backward of simple_coeffs in one launch (csrc/simple_coeffs_bwd.hip): dcoef in coef's layout ->
         (S [C, C], t [C], dWq, dbq, dWk, dbk, dWv | None, dbv | None): dx = x S + 1 t^T through the record."""
         dev = _require_device(record, Wq, bq, Wk, bk, Wv, bv, coef, dcoef)
-        ws_ = [None if t_ is None else _f32(t_, "weight").contiguous() for t_ in (Wq, bq, Wk, bk, Wv, bv)]
+        ws_ = _contig(Wq, bq, Wk, bk, Wv, bv, f32="weight")
         if dcoef.numel() < D * C + D + C + 1 or not dcoef.is_contiguous():
             raise TypeError("difformer_amd: dcoef must be contiguous with coef's layout [D*C | D | C | 1]")
         out = torch.empty(self.lib.dif_simple_coeffs_bwd_len(C, D), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_simple_coeffs_f32", dev):
-            rc = self.lib.dif_simple_coeffs_bwd_f32(_ptr(record), int(n_global), C, D, *[_ptr(t_) for t_ in ws_],
-                                                    float(attn_scale), _ptr(_f32(coef, "coef")), _ptr(_f32(dcoef, "dcoef")),
-                                                    _ptr(out), _stream(dev))
-        _lib.check(rc, "dif_simple_coeffs_bwd_f32")
+        self._call("dif_simple_coeffs_f32", "dif_simple_coeffs_bwd_f32", dev, _ptr(record), int(n_global), C, D,
+                   *[_ptr(t_) for t_ in ws_], float(attn_scale), _ptr(_f32(coef, "coef")), _ptr(_f32(dcoef, "dcoef")),
+                   _ptr(out))
         o = 0
         parts = []
         for shape in ((C, C), (C,), (D, C), (D,), (D, C), (D,), (D, C), (D,)):
@@ -840,103 +787,63 @@ class HipBackend:
         gather = (rowptr, src, val) of a one-block CSR over the same n nodes: the aggregation runs inside the layer kernel
         (no `ax`, no `row_sums`, no next-layer products)."""
         dev = _require_device(x, coef, ax, Wv, bv, row_sums, x0, ln_weight, ln_bias)
-        if gather is not None:
-            return self._simple_layer_gather(x, coef, D, gather, Wv, bv, gcn_scale, x0, residual, alpha, ln_weight, ln_bias,
-                                             eps, relu, head, ax is not None or next_plan is not None)
-        dt, sfx = _storage(x, ax, x0)              # activations: float32 or bfloat16; parameters always float32 here
-        for t_, nm in ((coef, "coef"), (Wv, "Wv"), (bv, "bv"), (ln_weight, "ln_weight"), (ln_bias, "ln_bias"), (row_sums, "row_sums")):
-            if t_ is not None:
-                _f32(t_, nm)
         n, C = x.shape
-        x, ldx = _row_major(x, C)
-        if ldx % 4 or x.data_ptr() % (4 * x.element_size()):
-            x, ldx = x.contiguous(), C
-        ldax = ldx0 = 0
-        if ax is not None:
-            ax, ldax = _row_major(ax, C)
-        if x0 is not None:
-            x0, ldx0 = _row_major(x0, D)
-        if Wv is not None:
-            Wv, bv = Wv.contiguous(), bv.contiguous()
-        if ln_weight is not None:
-            ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
+        if gather is not None:
+            rowptr, src, val = gather
+            if (ax is not None or next_plan is not None or rowptr.numel() != n + 1 or rowptr.dtype != torch.int32 or
+                    src.dtype != torch.int32):
+                raise TypeError("difformer_amd: the in-kernel aggregation takes an int32 one-block CSR over the rows of x "
+                                "and neither ax nor next-layer products")
+            _f32(val, "val")
+            row_sums = None
+        dt, sfx = _storage(x, ax, x0)              # activations: float32 or bfloat16; parameters always float32 here
+        _all_f32(coef=coef, Wv=Wv, bv=bv, ln_weight=ln_weight, ln_bias=ln_bias, row_sums=row_sums)
+        x, ldx = _rows(x, C, align=True)
+        ax, ldax = _rows(ax, C)
+        x0, ldx0 = _rows(x0, D)
+        Wv, bv, ln_weight, ln_bias = _contig(Wv, bv, ln_weight, ln_bias)
+        Wo = bo = None
+        Co = 0
         if head is not None:
-            Wo, bo = (_f32(t_, "head").contiguous() for t_ in head)          # float32 (exact copies of bf16 parameters)
+            Wo, bo = _contig(*head, f32="head")                              # float32 (exact copies of bf16 parameters)
             Co = Wo.shape[0]
             if next_plan is not None or Co > 128 or Wo.shape[1] != D:
                 raise TypeError("difformer_amd: the fused output Linear needs Co <= 128 and no next-layer products")
+        # the argument runs that every symbol of the family shares: x ... coef in front, gcn_scale ... relu behind the
+        # aggregation's operands
+        front = (_ptr(x), ldx, n, C, D, _ptr(coef))
+        tail = (float(gcn_scale), _ptr(x0), ldx0, int(bool(residual)), float(alpha), _ptr(ln_weight), _ptr(ln_bias),
+                float(eps), int(bool(relu)))
+        if gather is not None:
+            csr = (_ptr(rowptr), _ptr(src), _ptr(val), _ptr(Wv), _ptr(bv))
+            return self._simple_layer_gather(dev, dt, sfx, n, D, front + csr + tail, Wo, bo, Co)
+        args = front + (_ptr(ax), ldax, _ptr(Wv), _ptr(bv), _ptr(row_sums)) + tail
+        if head is not None:
             logits = torch.empty((n, Co), dtype=dt, device=dev)
-            fn = self.lib.dif_simple_layer_head_bf16 if sfx == "bf16" else self.lib.dif_simple_layer_head_f32
-            with _timed(self, "dif_simple_layer_f32", dev):
-                rc = fn(_ptr(x), ldx, n, C, D, _ptr(coef), _ptr(ax), ldax, _ptr(Wv), _ptr(bv),
-                        _ptr(row_sums), float(gcn_scale), _ptr(x0), ldx0, int(bool(residual)),
-                        float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps),
-                        int(bool(relu)), None, 0, _ptr(Wo), _ptr(bo), Co, _ptr(logits), Co,
-                        _stream(dev))
-            _lib.check(rc, "dif_simple_layer_head")
+            self._call("dif_simple_layer_f32", "dif_simple_layer_head_" + sfx, dev, *args, None, 0, _ptr(Wo), _ptr(bo), Co,
+                       _ptr(logits), Co)
             return logits
         out = torch.empty((n, D), dtype=dt, device=dev)
-        ys = None
         if sfx == "bf16":
             if next_plan is not None:
                 raise TypeError("difformer_amd: products for the next layer are float32-only")
-            with _timed(self, "dif_simple_layer_f32", dev):
-                rc = self.lib.dif_simple_layer_bf16(_ptr(x), ldx, n, C, D, _ptr(coef), _ptr(ax), ldax, _ptr(Wv), _ptr(bv),
-                                                    _ptr(row_sums), float(gcn_scale), _ptr(x0), ldx0, int(bool(residual)),
-                                                    float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps),
-                                                    int(bool(relu)), _ptr(out), D, _stream(dev))
-            _lib.check(rc, "dif_simple_layer_bf16")
+            self._call("dif_simple_layer_f32", "dif_simple_layer_bf16", dev, *args, _ptr(out), D)
             return out
-        if next_plan is not None:
-            ys = torch.empty((D // 4, int(next_plan[6]) * int(next_plan[7]), 4), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_simple_layer_f32", dev):
-            rc = self.lib.dif_simple_layer_f32(_ptr(x), ldx, n, C, D, _ptr(coef), _ptr(ax), ldax, _ptr(Wv), _ptr(bv),
-                                               _ptr(row_sums), float(gcn_scale), _ptr(x0), ldx0, int(bool(residual)),
-                                               float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps), int(bool(relu)),
-                                               _ptr(out), D, _ptr(next_rowptr) if ys is not None else None,
-                                               next_plan if ys is not None else None, _ptr(ys), _stream(dev))
-        _lib.check(rc, "dif_simple_layer_f32")
+        ys = None if next_plan is None else _slice_major(D, next_plan, dev)
+        self._call("dif_simple_layer_f32", "dif_simple_layer_f32", dev, *args, _ptr(out), D,
+                   _ptr(next_rowptr) if ys is not None else None, next_plan if ys is not None else None, _ptr(ys))
         return out if next_plan is None else (out, ys)
 
-    def _simple_layer_gather(self, x, coef, D, gather, Wv, bv, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
-                             head, conflicting):
-        dev = x.device
-        dt, sfx = _storage(x, None, x0)
-        rowptr, src, val = gather
-        n, C = x.shape
-        if conflicting or rowptr.numel() != n + 1 or rowptr.dtype != torch.int32 or src.dtype != torch.int32:
-            raise TypeError("difformer_amd: the in-kernel aggregation takes an int32 one-block CSR over the rows of x and "
-                            "neither ax nor next-layer products")
-        for t_, nm in ((coef, "coef"), (Wv, "Wv"), (bv, "bv"), (ln_weight, "ln_weight"), (ln_bias, "ln_bias"), (val, "val")):
-            if t_ is not None:
-                _f32(t_, nm)
-        x, ldx = _row_major(x, C)
-        if ldx % 4 or x.data_ptr() % (4 * x.element_size()):
-            x, ldx = x.contiguous(), C
-        ldx0 = 0
-        if x0 is not None:
-            x0, ldx0 = _row_major(x0, D)
-        if Wv is not None:
-            Wv, bv = Wv.contiguous(), bv.contiguous()
-        if ln_weight is not None:
-            ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
-        Wo = bo = out = logits = None
-        Co = 0
-        if head is not None:
-            Wo, bo = (_f32(t_, "head").contiguous() for t_ in head)
-            Co = Wo.shape[0]
-            if Co > 128 or Wo.shape[1] != D:
-                raise TypeError("difformer_amd: the fused output Linear needs Co <= 128")
+    def _simple_layer_gather(self, dev, dt, sfx, n, D, args, Wo, bo, Co):
+        """The launch of simple_layer(gather=...): `args` up to `relu`, then the rows or, with a head, the logits."""
+        out = logits = None
+        if Wo is not None:
             logits = torch.empty((n, Co), dtype=dt, device=dev)
         else:
             out = torch.empty((n, D), dtype=dt, device=dev)
-        fn = self.lib.dif_simple_layer_gather_bf16 if sfx == "bf16" else self.lib.dif_simple_layer_gather_f32
-        with _timed(self, "dif_simple_layer_f32", dev):
-            rc = fn(_ptr(x), ldx, n, C, D, _ptr(coef), _ptr(rowptr), _ptr(src), _ptr(val), _ptr(Wv), _ptr(bv),
-                    float(gcn_scale), _ptr(x0), ldx0, int(bool(residual)), float(alpha), _ptr(ln_weight), _ptr(ln_bias),
-                    float(eps), int(bool(relu)), _ptr(out), D, _ptr(Wo), _ptr(bo), Co, _ptr(logits), Co, _stream(dev))
-        _lib.check(rc, "dif_simple_layer_gather")
-        return logits if head is not None else out
+        self._call("dif_simple_layer_f32", "dif_simple_layer_gather_" + sfx, dev, *args, _ptr(out), D, _ptr(Wo), _ptr(bo),
+                   Co, _ptr(logits), Co)
+        return logits if Wo is not None else out
 
     # ---- a3, dense unweighted graphs: feature-sliced product with LDS-staged sources (csrc/gcn_sliced.hip) ----------
     def sliced_plan(self, n_src, n_rows, F):
@@ -966,20 +873,16 @@ class HipBackend:
         lengths = torch.empty(G * NT * 4, **i32)
         table = torch.empty((R + 1) * panels * NT * W + 1, **i32)
         status = torch.empty(1, **i32)
-        with _timed(self, "dif_sliced_measure", dev):
-            rc = self.lib.dif_sliced_measure(_ptr(rowptr), _ptr(blkptr), _ptr(src), int(n_src), int(nnz), int(row_begin),
-                                             int(n_rows), int(F), plan, _ptr(order), _ptr(parts), n_pos, _ptr(srt),
-                                             _ptr(counts), _ptr(lengths), _ptr(table), _ptr(status), _stream(dev))
-        _lib.check(rc, "dif_sliced_measure")
+        self._call("dif_sliced_measure", "dif_sliced_measure", dev, _ptr(rowptr), _ptr(blkptr), _ptr(src), int(n_src),
+                   int(nnz), int(row_begin), int(n_rows), int(F), plan, _ptr(order), _ptr(parts), n_pos, _ptr(srt),
+                   _ptr(counts), _ptr(lengths), _ptr(table), _ptr(status))
         bad, n_blocks = (int(v) for v in torch.stack([status[0], table[-1]]).tolist())
         if bad:
             return None
         entries = torch.empty(512 * max(n_blocks, 1), dtype=torch.int16, device=dev)
-        with _timed(self, "dif_sliced_emit", dev):
-            rc = self.lib.dif_sliced_emit(_ptr(rowptr), _ptr(blkptr), int(n_src), int(row_begin), int(n_rows), int(F), plan,
-                                          _ptr(order), _ptr(parts), n_pos, _ptr(srt), _ptr(counts), _ptr(table),
-                                          max(n_blocks, 1), _ptr(entries), _stream(dev))
-        _lib.check(rc, "dif_sliced_emit")
+        self._call("dif_sliced_emit", "dif_sliced_emit", dev, _ptr(rowptr), _ptr(blkptr), int(n_src), int(row_begin),
+                   int(n_rows), int(F), plan, _ptr(order), _ptr(parts), n_pos, _ptr(srt), _ptr(counts), _ptr(table),
+                   max(n_blocks, 1), _ptr(entries))
         return entries, table
 
     def sliced_prescale(self, x, rowptr, n_src, plan, dinv=None):
@@ -987,35 +890,24 @@ class HipBackend:
         dev = _require_device(x, rowptr, dinv)
         _f32(x, "x")
         F = x.shape[1]
-        x, ldx = _row_major(x, F)
-        if ldx % 4 or x.data_ptr() % 16:
-            x, ldx = x.contiguous(), F
-        ys = torch.empty((F // 4, int(plan[6]) * int(plan[7]), 4), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_sliced_prescale_f32", dev):
-            rc = self.lib.dif_sliced_prescale_f32(_ptr(x), ldx, _ptr(rowptr), _ptr(dinv), int(n_src), F, plan, _ptr(ys),
-                                                  _stream(dev))
-        _lib.check(rc, "dif_sliced_prescale_f32")
+        x, ldx = _rows(x, F, align=True)
+        ys = _slice_major(F, plan, dev)
+        self._call("dif_sliced_prescale_f32", "dif_sliced_prescale_f32", dev, _ptr(x), ldx, _ptr(rowptr), _ptr(dinv),
+                   int(n_src), F, plan, _ptr(ys))
         return ys
 
     def sliced_spmm(self, sl, ys, rowptr, n_src, row_begin, n_rows, F, attn=None, attn_scale=1.0, gcn_scale=1.0, dinv=None):
         """sl: the format (ops.SlicedAdjacency: entries, table, plan, order, parts, n_pos) built for these rows."""
         dev = _require_device(sl.entries, sl.table, ys, rowptr, attn, sl.order, sl.parts, dinv)
-        lda = 0
-        if attn is not None:
-            _f32(attn, "attn")
-            attn, lda = _row_major(attn, F)
-            if lda % 4 or attn.data_ptr() % 16:
-                attn, lda = attn.contiguous(), F
+        _all_f32(attn=attn)
+        attn, lda = _rows(attn, F, align=True)
         out = torch.empty((n_rows, F), dtype=torch.float32, device=dev)
         n_pos = int(n_rows) if sl.n_pos is None else int(sl.n_pos)
         ws_bytes = self.lib.dif_sliced_spmm_workspace_bytes(int(n_src), n_pos, int(F))   # > 0: a row shard (source splits)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        with _timed(self, "dif_sliced_spmm_f32", dev):
-            rc = self.lib.dif_sliced_spmm_f32(_ptr(sl.entries), _ptr(sl.table), sl.plan, _ptr(ys), _ptr(rowptr), _ptr(dinv),
-                                              _ptr(sl.order), _ptr(sl.parts), n_pos, int(n_src), int(row_begin), int(n_rows),
-                                              int(F), _ptr(attn), lda, float(attn_scale), float(gcn_scale), _ptr(out), F,
-                                              _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_sliced_spmm_f32")
+        ws = _workspace(ws_bytes, dev, or_none=True)
+        self._call("dif_sliced_spmm_f32", "dif_sliced_spmm_f32", dev, _ptr(sl.entries), _ptr(sl.table), sl.plan, _ptr(ys),
+                   _ptr(rowptr), _ptr(dinv), _ptr(sl.order), _ptr(sl.parts), n_pos, int(n_src), int(row_begin), int(n_rows),
+                   int(F), _ptr(attn), lda, float(attn_scale), float(gcn_scale), _ptr(out), F, _ptr(ws), ws_bytes)
         return out
 
     def row_order(self, rowptr, row_begin, n_rows):
@@ -1025,11 +917,9 @@ class HipBackend:
         order = torch.empty(n_rows, dtype=torch.int32, device=dev)
         stats = torch.empty(2, dtype=torch.int32, device=dev)
         ws_bytes = self.lib.dif_row_order_workspace_bytes(n_rows)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_row_order", dev):
-            rc = self.lib.dif_row_order(_ptr(rowptr), row_begin, n_rows, _ptr(order), _ptr(stats), _ptr(ws), ws_bytes,
-                                        _stream(dev))
-        _lib.check(rc, "dif_row_order")
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_row_order", "dif_row_order", dev, _ptr(rowptr), row_begin, n_rows, _ptr(order), _ptr(stats),
+                   _ptr(ws), ws_bytes)
         return order, stats
 
     # ---- a5 ends: narrow Linear (+ LayerNorm + ReLU) -------------------------------------------
@@ -1038,71 +928,61 @@ class HipBackend:
         n, C = x.shape
         Co = weight.shape[0]
         dt, sfx = _storage(x, weight, bias, ln_weight, ln_bias)
-        x, ldx = _row_major(x, C)
-        if C > 128 and (ldx % 4 or x.data_ptr() % (4 * x.element_size())):      # long rows: 4-element aligned rows
-            x, ldx = x.contiguous(), C
-        weight, bias = weight.contiguous(), bias.contiguous()
-        if ln_weight is not None:
-            ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
+        x, ldx = _rows(x, C, align=C > 128)                                      # long rows: 4-element aligned rows
+        weight, bias, ln_weight, ln_bias = _contig(weight, bias, ln_weight, ln_bias)
         out = torch.empty((n, Co), dtype=dt, device=dev)
         from . import ops
         if sfx == "f32" and Co > 64 and ops.linear_xwide_covers(x, weight):
             # wide rows into a wide layer: one product (C <= 416) or the two halves of the input channels as the two accumulating
             # products of the hidden-300 layer kernel; weights packed once per parameter version
-            if ldx % 4 or x.data_ptr() % 16:
-                x, ldx = x.contiguous(), C
+            x, ldx = _rows(x, C, align=True)
             two = C > ops.XWIDE_MAX
             Ch = C // 2 if two else C
             pa = self.xwide_pack(weight, False, Ch, Co, cache=True)
             pb = self.xwide_pack(weight, False, Ch, Co, cache=True, col0=Ch) if two else None
-            with _timed(self, "dif_linear_f32", dev):
-                rc = self.lib.dif_linear_xwide_f32(_ptr(x), ldx, n, C, _ptr(pa), _ptr(pb), _ptr(bias), Co, _ptr(ln_weight), _ptr(ln_bias),
-                                                   float(eps), int(bool(relu)), _ptr(out), Co, _stream(dev))
-            _lib.check(rc, "dif_linear_xwide_f32")
-            return out
-        if (sfx == "f32" and C > 128 and Co <= 64 and C <= 8192 and not ops.EXACT_FP32 and
+            symbol, mats = "dif_linear_xwide_f32", (_ptr(pa), _ptr(pb))
+        elif (sfx == "f32" and C > 128 and Co <= 64 and C <= 8192 and not ops.EXACT_FP32 and
                 (n < 16384 or C % 4 or ldx % 4 or x.data_ptr() % 16 or weight.data_ptr() % 16)):
             # few rows, or rows that are only 4-byte aligned (Cora: 2,708 x 1,433): K split over the waves of a workgroup,
             # the weights packed once per parameter version (bfloat16 hi / lo parts in MFMA fragment order)
             packed = self._packed_weight(weight, C, Co, dev)
-            with _timed(self, "dif_linear_f32", dev):
-                rc = self.lib.dif_linear_packed_f32(_ptr(x), ldx, n, C, _ptr(packed), _ptr(bias), Co, _ptr(ln_weight), _ptr(ln_bias),
-                                                    float(eps), int(bool(relu)), _ptr(out), Co, _stream(dev))
-            _lib.check(rc, "dif_linear_packed_f32")
-            return out
-        fn = getattr(self.lib, "dif_linear_" + sfx)
-        with _timed(self, "dif_linear_f32", dev):
-            rc = fn(_ptr(x), ldx, n, C, _ptr(weight), _ptr(bias), Co, _ptr(ln_weight), _ptr(ln_bias), float(eps),
-                    int(bool(relu)), _ptr(out), Co, _stream(dev))
-        _lib.check(rc, "dif_linear_" + sfx)
+            symbol, mats = "dif_linear_packed_f32", (_ptr(packed),)
+        else:
+            symbol, mats = "dif_linear_" + sfx, (_ptr(weight),)
+        self._call("dif_linear_f32", symbol, dev, _ptr(x), ldx, n, C, *mats, _ptr(bias), Co, _ptr(ln_weight), _ptr(ln_bias),
+                   float(eps), int(bool(relu)), _ptr(out), Co)
         return out
 
-    def _packed_weight(self, weight, C, Co, dev):
-        """dif_linear_pack_f32 of a [Co, C] float32 weight, cached per tensor (identity through a weak reference + data_ptr +
-        version, like the CSR cache: a new tensor at a recycled address must not find the old packing): rebuilt after
-        optimiser steps / load_state_dict (they bump the version); `.data` writes need model.invalidate_caches()."""
-        import weakref
+    def _cached_pack(self, tensor, geometry, pack):
+        """pack() -> packed copy of a weight `tensor`, cached per tensor and `geometry` (a tuple): identity through a weak
+        reference + data_ptr + version, like the CSR cache (a new tensor at a recycled address must not find the old
+        packing).  Rebuilt after optimiser steps / load_state_dict (they bump the version); `.data` writes need
+        model.invalidate_caches(); a tensor without a version (< 0) is packed every time."""
         from . import ops
-        ver = ops.tensor_version(weight)
-        key = (id(weight), weight.data_ptr(), ver, C, Co, str(dev))
+        ver = ops.tensor_version(tensor)
+        key = (id(tensor), tensor.data_ptr(), ver) + geometry
         cache = self.__dict__.setdefault("_packed", {})
         hit = cache.get(key)
-        if hit is not None and ver >= 0 and hit[0]() is weight:
+        if hit is not None and ver >= 0 and hit[0]() is tensor:
             return self._pin(hit[1])
-        packed = torch.empty(self.lib.dif_linear_packed_bytes(C), dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_linear_pack_f32", dev):
-            rc = self.lib.dif_linear_pack_f32(_ptr(weight), C, Co, _ptr(packed), _stream(dev))
-        _lib.check(rc, "dif_linear_pack_f32")
+        packed = pack()
         if ver >= 0:
-            self._packed_insert(cache, key, weight, packed)
+            self._packed_insert(cache, key, tensor, packed)
         return self._pin(packed)
+
+    def _packed_weight(self, weight, C, Co, dev):
+        """dif_linear_pack_f32 of a [Co, C] float32 weight, once per parameter version (_cached_pack)."""
+        def pack():
+            packed = torch.empty(self.lib.dif_linear_packed_bytes(C), dtype=torch.uint8, device=dev)
+            self._call("dif_linear_pack_f32", "dif_linear_pack_f32", dev, _ptr(weight), C, Co, _ptr(packed))
+            return packed
+        return self._cached_pack(weight, (C, Co, str(dev)), pack)
 
     @staticmethod
     def _packed_insert(cache, key, tensor, packed):
         """Insert into a packed-weight cache.  Evicted: entries of freed tensors and OLDER VERSIONS of this tensor (an optimiser
         step per epoch would otherwise add an entry per epoch); beyond 64 live entries the oldest.  Never everything at once:
         a captured hipGraph bakes raw pointers to these buffers in (it pins the ones it used itself, `capture_pins`)."""
-        import weakref
         for k in [k for k, v in cache.items() if v[0]() is None or (v[0]() is tensor and k[:2] == key[:2] and k[3:] == key[3:])]:
             del cache[k]
         while len(cache) >= 64:
@@ -1128,11 +1008,8 @@ class HipBackend:
             return None
         conv, ldc = _row_major(conv, H * D)
         g, ldg = _row_major(grad_out, D)
-        ldx0 = ldp = 0
-        if x0 is not None:
-            x0, ldx0 = _row_major(x0, D)
-        if prev is not None:
-            prev, ldp = _row_major(prev, D)
+        x0, ldx0 = _rows(x0, D)
+        prev, ldp = _rows(prev, D)
         if any(ld % 4 for ld in (ldc, ldg, ldx0, ldp)) or any(t is not None and t.data_ptr() % 16 for t in (conv, g, x0, prev)):
             return None
         f32 = dict(dtype=torch.float32, device=dev)
@@ -1145,13 +1022,10 @@ class HipBackend:
             ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
             d_ln = torch.empty(2 * D, **f32)
             ws_bytes = self.lib.dif_layer_tail_bwd_workspace_bytes(n, D)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_layer_tail_bwd_f32", dev):
-            rc = self.lib.dif_layer_tail_bwd_f32(_ptr(conv), ldc, n, H, D, _ptr(x0), ldx0, _ptr(prev), ldp, float(alpha),
-                                                 _ptr(ln_weight), _ptr(ln_bias), float(eps), int(bool(relu)), _ptr(g), ldg,
-                                                 _ptr(d_conv), H * D, _ptr(d_x0), D, _ptr(d_prev), D, _ptr(d_ln), _ptr(ws),
-                                                 ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_layer_tail_bwd_f32")
+            ws = _workspace(ws_bytes, dev)
+        self._call("dif_layer_tail_bwd_f32", "dif_layer_tail_bwd_f32", dev, _ptr(conv), ldc, n, H, D, _ptr(x0), ldx0,
+                   _ptr(prev), ldp, float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps), int(bool(relu)), _ptr(g), ldg,
+                   _ptr(d_conv), H * D, _ptr(d_x0), D, _ptr(d_prev), D, _ptr(d_ln), _ptr(ws), ws_bytes)
         return (d_conv, d_x0, d_prev, None if d_ln is None else d_ln[:D], None if d_ln is None else d_ln[D:2 * D])
 
     def coeffs_bg(self, x, record, n_global, factors, C, D, attn_scale):
@@ -1169,18 +1043,14 @@ class HipBackend:
             n = x.shape[0]
             x, ldx = _row_major(x, C)
             ws_bytes = self.lib.dif_gram_bg_workspace_bytes(n, C)
-            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            ws = _workspace(ws_bytes, dev, floor=16)
             xp = x
-        with _timed(self, "dif_gram_bg_f32", dev):
-            rc = self.lib.dif_gram_bg_f32(_ptr(xp), ldx, n, C, int(n_global), _ptr(factors.st), _ptr(gt), _ptr(ws), ws_bytes,
-                                          _stream(dev))
-        _lib.check(rc, "dif_gram_bg_f32")
+        self._call("dif_gram_bg_f32", "dif_gram_bg_f32", dev, _ptr(xp), ldx, n, C, int(n_global), _ptr(factors.st), _ptr(gt),
+                   _ptr(ws), ws_bytes)
         scratch = torch.empty(80 * 80 + 4, **f32)
         coef = torch.empty(self.lib.dif_simple_coeffs_len(C, D), **f32)
-        with _timed(self, "dif_simple_coeffs_bg_f32", dev):
-            rc = self.lib.dif_simple_coeffs_bg_f32(_ptr(gt), _ptr(factors.pt), _ptr(factors.vtt), _ptr(factors.st), C, D,
-                                                   float(attn_scale), _ptr(scratch), _ptr(coef), _stream(dev))
-        _lib.check(rc, "dif_simple_coeffs_bg_f32")
+        self._call("dif_simple_coeffs_bg_f32", "dif_simple_coeffs_bg_f32", dev, _ptr(gt), _ptr(factors.pt), _ptr(factors.vtt),
+                   _ptr(factors.st), C, D, float(attn_scale), _ptr(scratch), _ptr(coef))
         return coef
 
     def gram_sym(self, x):
@@ -1194,17 +1064,12 @@ class HipBackend:
         from . import ops
         if 64 < C <= 128 and C % 4 == 0 and ldx % 4 == 0 and x.data_ptr() % 16 == 0 and (ops.EXACT_FP32 or n < 4096):
             # hidden 128: one pass over x with the whole upper half of X^T X in a wave's registers (csrc/simple_layer_wide.hip)
-            ws_bytes = self.lib.dif_gram128_workspace_bytes(n, C)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            with _timed(self, "dif_gram_sym_f32", dev):
-                rc = self.lib.dif_gram128_f32(_ptr(x), ldx, n, C, _ptr(rec), _ptr(ws), ws_bytes, _stream(dev))
-            _lib.check(rc, "dif_gram128_f32")
-            return rec
-        ws_bytes = self.lib.dif_gram_sym_workspace_bytes(n, C)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_gram_sym_f32", dev):
-            rc = self.lib.dif_gram_sym_f32(_ptr(x), ldx, n, C, _ptr(rec), _ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, "dif_gram_sym_f32")
+            ws_fn, symbol = self.lib.dif_gram128_workspace_bytes, "dif_gram128_f32"
+        else:
+            ws_fn, symbol = self.lib.dif_gram_sym_workspace_bytes, "dif_gram_sym_f32"
+        ws_bytes = ws_fn(n, C)
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_gram_sym_f32", symbol, dev, _ptr(x), ldx, n, C, _ptr(rec), _ptr(ws), ws_bytes)
         return rec
 
     def wide_coeffs(self, rec, C, n_global, S, V, P):
@@ -1216,10 +1081,8 @@ class HipBackend:
         partial = torch.empty(2 * ((C + 16) // 16), dtype=torch.float64, device=dev)
         B = torch.empty((C, DV), dtype=torch.float32, device=dev)
         bias = torch.empty(DV, dtype=torch.float32, device=dev)
-        with _timed(self, "dif_wide_coeffs_f64", dev):
-            rc = self.lib.dif_wide_coeffs_f64(_ptr(rec), C, int(n_global), _ptr(S), _ptr(V), _ptr(P), DV, _ptr(T), _ptr(partial),
-                                              _ptr(B), _ptr(bias), _stream(dev))
-        _lib.check(rc, "dif_wide_coeffs_f64")
+        self._call("dif_wide_coeffs_f64", "dif_wide_coeffs_f64", dev, _ptr(rec), C, int(n_global), _ptr(S), _ptr(V), _ptr(P),
+                   DV, _ptr(T), _ptr(partial), _ptr(B), _ptr(bias))
         return B, bias
 
     def layer_tail_mix(self, Z, D, den_col, conv_scale, add, add_scale, rs, bv, x0, prev, alpha, ln_weight, ln_bias, eps,
@@ -1228,149 +1091,83 @@ class HipBackend:
         numerator in columns [0, D) and the denominator in column den_col; add [n, D] / rs [n] / bv [D] optional."""
         dev = _require_device(Z, add, rs, bv, x0, prev, ln_weight, ln_bias)
         n, ldz = Z.shape
-        for t_, nm in ((Z, "Z"), (add, "add"), (rs, "rs"), (bv, "bv"), (x0, "x0"), (prev, "prev")):
-            if t_ is not None:
-                _f32(t_, nm)
+        _all_f32(Z=Z, add=add, rs=rs, bv=bv, x0=x0, prev=prev)
         if not Z.is_contiguous() or ldz % 4:
             raise ValueError("difformer_amd: layer_tail_mix needs a contiguous Z with a row length that is a multiple of 4")
-        lda = ldx0 = ldp = 0
-        if add is not None:
-            add, lda = _row_major(add, D)
-        if x0 is not None:
-            x0, ldx0 = _row_major(x0, D)
-        if prev is not None:
-            prev, ldp = _row_major(prev, D)
-        if ln_weight is not None:
-            ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
-        if rs is not None:
-            rs, bv = rs.contiguous(), bv.contiguous()
+        add, lda = _rows(add, D)
+        x0, ldx0 = _rows(x0, D)
+        prev, ldp = _rows(prev, D)
+        ln_weight, ln_bias, rs, bv = _contig(ln_weight, ln_bias, rs, bv)
         out = torch.empty((n, D), dtype=torch.float32, device=dev)
         den_ptr = None if den_col is None else Z.data_ptr() + 4 * int(den_col)
-        with _timed(self, "dif_layer_tail_mix_f32", dev):
-            rc = self.lib.dif_layer_tail_mix_f32(_ptr(Z), ldz, den_ptr, ldz, float(conv_scale), _ptr(add), lda,
-                                                 float(add_scale), _ptr(rs), _ptr(bv), n, D, _ptr(x0), ldx0, _ptr(prev), ldp,
-                                                 float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps), int(bool(relu)),
-                                                 _ptr(out), D, _stream(dev))
-        _lib.check(rc, "dif_layer_tail_mix_f32")
+        self._call("dif_layer_tail_mix_f32", "dif_layer_tail_mix_f32", dev, _ptr(Z), ldz, den_ptr, ldz, float(conv_scale),
+                   _ptr(add), lda, float(add_scale), _ptr(rs), _ptr(bv), n, D, _ptr(x0), ldx0, _ptr(prev), ldp, float(alpha),
+                   _ptr(ln_weight), _ptr(ln_bias), float(eps), int(bool(relu)), _ptr(out), D)
         return out
 
     def simple_layer_wide(self, x, B, bias, D, attn_scale, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias,
                           eps, relu=False):
         """Closed-form `simple` layer for 64 < max(C, D) <= 128 in one pass (csrc/simple_layer_wide.hip): x [n, C], B [C, dv]
         = [Mn | u | ...], bias [dv] = [cn | cd | ...] (wide_coeffs), ax = A_hat x [n, C] or None, Wv [D, C] / bv [D] / rs [n]."""
+        return self._simple_layer_wide(False, x, B, bias, D, attn_scale, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha,
+                                       ln_weight, ln_bias, eps, relu)
+
+    def simple_layer_xwide(self, x, B, bias, D, attn_scale, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias,
+                           eps, relu=False):
+        """Closed-form `simple` layer for 128 < max(C, D) <= 416 in one pass (csrc/simple_layer_xwide.hip); arguments as
+        simple_layer_wide.  Mn is packed per call (it changes with the Gram record), Wv once per parameter version."""
+        return self._simple_layer_wide(True, x, B, bias, D, attn_scale, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha,
+                                       ln_weight, ln_bias, eps, relu)
+
+    def _simple_layer_wide(self, xwide, x, B, bias, D, attn_scale, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight,
+                           ln_bias, eps, relu):
+        """Both wide layer kernels: the same operands, but the xwide one takes Mn and Wv as packed MFMA fragments."""
         dev = _require_device(x, B, bias, ax, Wv, bv, rs, x0, ln_weight, ln_bias)
         n, C = x.shape
-        for t_, nm in ((x, "x"), (B, "B"), (bias, "bias"), (ax, "ax"), (Wv, "Wv"), (x0, "x0")):
-            if t_ is not None:
-                _f32(t_, nm)
-        x, ldx = _row_major(x, C)
-        if ldx % 4 or x.data_ptr() % 16:
-            x, ldx = x.contiguous(), C
-        B, bias = B.contiguous(), bias.contiguous()
-        ldax = ldx0 = 0
-        if ax is not None:
-            ax, ldax = _row_major(ax, C)
-            if ldax % 4 or ax.data_ptr() % 16:
-                ax, ldax = ax.contiguous(), C
-        if x0 is not None:
-            x0, ldx0 = _row_major(x0, D)
-            if ldx0 % 4 or x0.data_ptr() % 16:
-                x0, ldx0 = x0.contiguous(), D
-        if Wv is not None:
-            Wv, bv = Wv.contiguous(), bv.contiguous()
-        if rs is not None:
-            rs = rs.contiguous()
-        if ln_weight is not None:
-            ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
+        _all_f32(x=x, B=B, bias=bias, ax=ax, Wv=Wv, x0=x0)
+        x, ldx = _rows(x, C, align=True)
+        ax, ldax = _rows(ax, C, align=True)
+        x0, ldx0 = _rows(x0, D, align=True)
+        B, bias, bv, rs, ln_weight, ln_bias = _contig(B, bias, bv, rs, ln_weight, ln_bias)
+        coeffs = (_ptr(B), int(B.shape[1]), _ptr(bias), float(attn_scale), _ptr(ax), ldax)
+        if xwide:
+            pm = self.xwide_pack(B, True, C, D)
+            pv = None if Wv is None else self.xwide_pack(Wv, False, C, D, cache=True)
+            symbol, mats = "dif_simple_layer_xwide_f32", (_ptr(pm), _ptr(pv)) + coeffs
+        else:
+            Wv, = _contig(Wv)
+            symbol, mats = "dif_simple_layer_wide_f32", coeffs + (_ptr(Wv),)
         out = torch.empty((n, D), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_simple_layer_f32", dev):
-            rc = self.lib.dif_simple_layer_wide_f32(_ptr(x), ldx, n, C, D, _ptr(B), int(B.shape[1]), _ptr(bias), float(attn_scale),
-                                                    _ptr(ax), ldax, _ptr(Wv), _ptr(bv), _ptr(rs), float(gcn_scale), _ptr(x0), ldx0,
-                                                    int(bool(residual)), float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps),
-                                                    int(bool(relu)), _ptr(out), D, _stream(dev))
-        _lib.check(rc, "dif_simple_layer_wide_f32")
+        self._call("dif_simple_layer_f32", symbol, dev, _ptr(x), ldx, n, C, D, *mats, _ptr(bv), _ptr(rs), float(gcn_scale),
+                   _ptr(x0), ldx0, int(bool(residual)), float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps),
+                   int(bool(relu)), _ptr(out), D)
         return out
 
     def xwide_pack(self, src, transposed, C, D, cache=False, col0=0):
         """dif_xwide_pack_f32: src [C, ld] (transposed: the [Mn | u] operand) or [D, ld] (an nn.Linear weight; col0: the C
         input channels start at that column) -> packed MFMA fragments.  cache=True keeps the packing per weight tensor
         (identity + version, as _packed_weight)."""
-        import weakref
-        from . import ops
         dev = src.device
-        key = None
-        if cache:
-            ver = ops.tensor_version(src)
-            key = (id(src), src.data_ptr(), ver, C, D, bool(transposed), str(dev), col0)
-            store = self.__dict__.setdefault("_packed", {})
-            hit = store.get(key)
-            if hit is not None and ver >= 0 and hit[0]() is src:
-                return self._pin(hit[1])
-        src_c = src.contiguous()
-        packed = torch.empty(self.lib.dif_xwide_packed_bytes(C, D), dtype=torch.uint8, device=dev)
-        with _timed(self, "dif_xwide_pack_f32", dev):
-            rc = self.lib.dif_xwide_pack_f32(src_c.data_ptr() + 4 * col0, int(src_c.shape[1]), int(bool(transposed)), C, D, _ptr(packed),
-                                             _stream(dev))
-        _lib.check(rc, "dif_xwide_pack_f32")
-        if cache and key[2] >= 0:
-            self._packed_insert(store, key, src, packed)
-        return self._pin(packed)
 
-    def simple_layer_xwide(self, x, B, bias, D, attn_scale, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias,
-                           eps, relu=False):
-        """Closed-form `simple` layer for 128 < max(C, D) <= 416 in one pass (csrc/simple_layer_xwide.hip); arguments as
-        simple_layer_wide.  Mn is packed per call (it changes with the Gram record), Wv once per parameter version."""
-        dev = _require_device(x, B, bias, ax, Wv, bv, rs, x0, ln_weight, ln_bias)
-        n, C = x.shape
-        for t_, nm in ((x, "x"), (B, "B"), (bias, "bias"), (ax, "ax"), (Wv, "Wv"), (x0, "x0")):
-            if t_ is not None:
-                _f32(t_, nm)
-        x, ldx = _row_major(x, C)
-        if ldx % 4 or x.data_ptr() % 16:
-            x, ldx = x.contiguous(), C
-        B, bias = B.contiguous(), bias.contiguous()
-        ldax = ldx0 = 0
-        if ax is not None:
-            ax, ldax = _row_major(ax, C)
-            if ldax % 4 or ax.data_ptr() % 16:
-                ax, ldax = ax.contiguous(), C
-        if x0 is not None:
-            x0, ldx0 = _row_major(x0, D)
-            if ldx0 % 4 or x0.data_ptr() % 16:
-                x0, ldx0 = x0.contiguous(), D
-        pm = self.xwide_pack(B, True, C, D)
-        pv = None
-        if Wv is not None:
-            pv, bv = self.xwide_pack(Wv, False, C, D, cache=True), bv.contiguous()
-        if rs is not None:
-            rs = rs.contiguous()
-        if ln_weight is not None:
-            ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
-        out = torch.empty((n, D), dtype=torch.float32, device=dev)
-        with _timed(self, "dif_simple_layer_f32", dev):
-            rc = self.lib.dif_simple_layer_xwide_f32(_ptr(x), ldx, n, C, D, _ptr(pm), _ptr(pv), _ptr(B), int(B.shape[1]), _ptr(bias),
-                                                     float(attn_scale), _ptr(ax), ldax, _ptr(bv), _ptr(rs), float(gcn_scale), _ptr(x0),
-                                                     ldx0, int(bool(residual)), float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps),
-                                                     int(bool(relu)), _ptr(out), D, _stream(dev))
-        _lib.check(rc, "dif_simple_layer_xwide_f32")
-        return out
+        def pack():
+            src_c = src.contiguous()
+            packed = torch.empty(self.lib.dif_xwide_packed_bytes(C, D), dtype=torch.uint8, device=dev)
+            self._call("dif_xwide_pack_f32", "dif_xwide_pack_f32", dev, src_c.data_ptr() + 4 * col0, int(src_c.shape[1]),
+                       int(bool(transposed)), C, D, _ptr(packed))
+            return packed
+        if cache:
+            return self._cached_pack(src, (C, D, bool(transposed), str(dev), col0), pack)
+        return self._pin(pack())
 
     def layer_tail(self, conv, x0, prev, alpha, ln_weight, ln_bias, eps, relu=False):
         dev = _require_device(conv, x0, prev, ln_weight, ln_bias)
         n, H, D = conv.shape
         dt, sfx = _storage(conv, x0, prev, ln_weight, ln_bias)
         conv, ldc = _row_major(conv, H * D)
-        ldx0 = ldp = 0
-        if x0 is not None:
-            x0, ldx0 = _row_major(x0, D)
-        if prev is not None:
-            prev, ldp = _row_major(prev, D)
-        if ln_weight is not None:
-            ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
+        x0, ldx0 = _rows(x0, D)
+        prev, ldp = _rows(prev, D)
+        ln_weight, ln_bias = _contig(ln_weight, ln_bias)
         out = torch.empty((n, D), dtype=dt, device=dev)
-        fn = getattr(self.lib, "dif_layer_tail_" + sfx)
-        with _timed(self, "dif_layer_tail_f32", dev):
-            rc = fn(_ptr(conv), ldc, n, H, D, _ptr(x0), ldx0, _ptr(prev), ldp, float(alpha), _ptr(ln_weight),
-                    _ptr(ln_bias), float(eps), int(bool(relu)), _ptr(out), D, _stream(dev))
-        _lib.check(rc, "dif_layer_tail_" + sfx)
+        self._call("dif_layer_tail_f32", "dif_layer_tail_" + sfx, dev, _ptr(conv), ldc, n, H, D, _ptr(x0), ldx0, _ptr(prev),
+                   ldp, float(alpha), _ptr(ln_weight), _ptr(ln_bias), float(eps), int(bool(relu)), _ptr(out), D)
         return out

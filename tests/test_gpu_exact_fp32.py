@@ -116,7 +116,7 @@ def test_output_linear_folded_into_the_last_layer(dev):
     check({m: rel_err(o, ref) for m, o in outs.items()}, 1.4e-6, "head folded into the last layer")
 
 
-# ================================================================== 3: long-row input Linear (csrc/skinny_linear.hip:917-948, backend_hip.py:1057)
+# ================================================================== 3: long-row input Linear (csrc/skinny_linear.hip:917-948, HipBackend.linear)
 @pytest.mark.parametrize("n,c_in,path,bound", [(32768, 300, "resident", 3.0e-6), (20000, 300, "chunked", 3.2e-6),
                                                (3000, 300, "packed", 1.0e-6), (20000, 301, "packed-unaligned", 1.1e-6)])
 def test_long_row_input_linear(n, c_in, path, bound, dev):
@@ -186,7 +186,7 @@ def test_wide_closed_form_layer_kernels(c, dev):
     check({m: rel_err(o, ref) for m, o in outs.items()}, 1.2e-6 if c <= 128 else 1.7e-6, f"wide closed-form layer C={c}")
 
 
-# ================================================================== 6: Gram record (csrc/simple_attn.hip:911, backend_hip.py:1189)
+# ================================================================== 6: Gram record (csrc/simple_attn.hip:911, HipBackend.gram_sym)
 @pytest.mark.parametrize("c", [128, 200])
 def test_gram_record(c, dev):
     """gram_slab_kernel (C > 64, >= 4,096 rows) through backend.gram_sym; at 65..128 columns the host picks dif_gram128_f32

@@ -174,6 +174,30 @@ def test_row_major_layout_helper():
     assert t.is_contiguous() and ld == 4
     t, ld = _row_major(torch.randn(1, 2, 4), 8)
     assert ld == 8
+    # _rows: the same for an optional operand, with the copy for kernels that read four elements at a time on request
+    from difformer_amd.backend_hip import _rows
+    assert _rows(None, 8) == (None, 0) and _rows(None, 8, align=True) == (None, 0)
+    base = torch.empty(4 * 64 + 64, dtype=torch.float32)
+    base = base[(-base.data_ptr() // 4) % 4:]                # the first element on a 16-byte boundary
+    assert base.data_ptr() % 16 == 0
+    wide = base[: 10 * 24].view(10, 24)
+    for align in (False, True):                             # aligned strided view: passes through, its stride is the ld
+        t, ld = _rows(wide[:, 8:16], 8, align=align)
+        assert t.data_ptr() == wide[:, 8:16].data_ptr() and ld == 24
+    off = wide[:, 1:9]                                      # starts 4 bytes off a 16-byte boundary
+    odd = base[: 10 * 22].view(10, 22)[:, :8]               # stride 22: no multiple of 4
+    for view in (off, odd):
+        t, ld = _rows(view, 8)
+        assert t.data_ptr() == view.data_ptr() and ld == view.stride(0)
+        t, ld = _rows(view, 8, align=True)
+        assert t.is_contiguous() and t.data_ptr() != view.data_ptr() and ld == 8 and torch.equal(t, view)
+    # bfloat16 rows are judged against 4 elements = 8 bytes: a start 8 bytes off a 16-byte boundary is aligned, 2 bytes is not
+    half = base.view(torch.bfloat16)[: 10 * 24].view(10, 24)
+    assert half[:, 4:12].data_ptr() % 16 == 8
+    t, ld = _rows(half[:, 4:12], 8, align=True)
+    assert t.data_ptr() == half[:, 4:12].data_ptr() and ld == 24
+    t, ld = _rows(half[:, 1:9], 8, align=True)
+    assert t.is_contiguous() and t.data_ptr() != half[:, 1:9].data_ptr() and ld == 8
 
 
 def test_cpu_operands_raise_without_fallback():
