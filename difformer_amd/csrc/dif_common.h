@@ -157,4 +157,79 @@ template <> struct Elem<bf16> {
 template <typename T>
 inline bool aligned_v4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0; }
 
+// ---- small device helpers shared by the kernels ----
+__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+
+// sigma(x) with the hardware exp2 / rcp (each ~1 ulp): far inside the 1e-4 parity budget, and ~5x
+// fewer VALU instructions than expf + IEEE division next to the MFMAs.  (Not tiny_common.h's IEEE sigmoidf nor
+// tiny_sigmoid_grid.hip's fast_sigmoid: those differ on purpose.)
+__device__ __forceinline__ float sigmoid_hw(float x) {
+    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+}
+
+// dinv = sqrt(1 / in-degree) as difformer.py:66-68; a node without incoming entries contributes nothing (nan_to_num of the
+// infinite value, :74).  The in-degree is the row length of the CSR.
+__device__ __forceinline__ float dinv_of(const int32_t* __restrict__ rowptr, int64_t row) {
+    const int32_t d = rowptr[row + 1] - rowptr[row];
+    return d > 0 ? sqrtf(1.0f / static_cast<float>(d)) : 0.f;
+}
+
+// one 16 x 16 tile of a 64 x 64 x 64 product on the fp32 MFMA: A(i, k), B(k, j) are LDS accessors;
+// lane holds D[16ti + 4lg + reg][16tj + l15]
+template <typename FA, typename FB>
+__device__ __forceinline__ f32x4 tile_product(FA A, FB B, int ti, int tj, int l15, int lg) {
+    f32x4 d = zero4();
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks)
+        d = __builtin_amdgcn_mfma_f32_16x16x4f32(A(16 * ti + l15, 4 * ks + lg), B(4 * ks + lg, 16 * tj + l15), d, 0, 0, 0);
+    return d;
+}
+
+// Branch-free fragment load: out-of-range rows / columns are read from a clamped (valid) address and
+// zeroed afterwards, so the compiler can issue all of a tile's loads back to back (a guarded load is
+// its own exec-masked branch region and serialises).
+template <bool VEC, typename T>
+__device__ __forceinline__ f32x4 ld4(const T* __restrict__ base, int64_t ld, int64_t rc, bool rok,
+                                     int col0, int c, int width) {
+    f32x4 z;
+    if (VEC) {
+        const bool cok = c < width;                       // width % 4 == 0 here
+        z = Elem<T>::ld4(base + rc * ld + col0 + (cok ? c : 0));
+        if (!(rok && cok)) z = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool cok = c + i < width;
+            const float t = Elem<T>::ld(base + rc * ld + col0 + (cok ? c + i : 0));
+            z[i] = (rok && cok) ? t : 0.f;
+        }
+    }
+    return z;
+}
+
+// The two halves of ld4 for software-pipelined loads: the raw (clamped-address) load is issued a step ahead and NOT touched until
+// the step that uses it -- a mask (or a branch) at issue time would make the issuing step wait for the data.
+template <bool VEC, typename T>
+__device__ __forceinline__ f32x4 ld4_raw(const T* __restrict__ base, int64_t ld, int64_t rc, int col0, int c, int width) {
+    f32x4 z;
+    if (VEC) {
+        z = Elem<T>::ld4(base + rc * ld + col0 + (c < width ? c : 0));
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) z[i] = Elem<T>::ld(base + rc * ld + col0 + (c + i < width ? c + i : 0));
+    }
+    return z;
+}
+template <bool VEC>
+__device__ __forceinline__ f32x4 mask4(f32x4 z, bool rok, int c, int width) {
+    if (VEC) {
+        if (!(rok && c < width)) z = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (!(rok && c + i < width)) z[i] = 0.f;
+    }
+    return z;
+}
+
 }  // namespace dif

@@ -34,6 +34,7 @@
 namespace {
 
 using dif::f32x4;
+using dif::dinv_of;
 
 // Geometry knobs of measurement builds (profiles/r03_experiments.md): the default is one 16-wave workgroup per CU with the
 // whole LDS; -DDIF_SLICED_TILE_ROWS=5104 -DDIF_SLICED_MAX_WAVES=8 -DDIF_SLICED_WG_PER_CU=2 builds two 8-wave workgroups
@@ -599,11 +600,6 @@ __global__ __launch_bounds__(1024) void sliced_table_kernel(const int32_t* __res
 // incoming entries contributes nothing (nan_to_num of the infinite value, :74).  The in-degree is the row length of
 // the CSR; for the ADJOINT product (CSR of the transposed graph, rows = sources) the caller passes the vector.
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float dinv_of(const int32_t* __restrict__ rowptr, int64_t row) {
-    const int32_t d = rowptr[row + 1] - rowptr[row];
-    return d > 0 ? sqrtf(1.0f / static_cast<float>(d)) : 0.f;
-}
-
 constexpr int kPreSlices = 32;      // slices per block of the prescale pass (LDS staging: 32 x 65 float4)
 
 __global__ __launch_bounds__(256) void sliced_prescale_kernel(const float* __restrict__ x, int64_t ldx,

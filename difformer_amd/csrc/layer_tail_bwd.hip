@@ -14,8 +14,7 @@
 namespace {
 
 using dif::f32x4;
-
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+using dif::zero4;
 
 // G lanes x V vectors of 4 elements hold one row (D <= 4 G V, D % 4 == 0; V = 2 with G = 64 for 257 .. 512 columns: hidden 300 / 400,
 // image and text/run.sh); 256 / G rows per workgroup pass.

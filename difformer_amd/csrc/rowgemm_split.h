@@ -1,11 +1,12 @@
 // Shared by csrc/simple_attn_bwd.hip (dif_rowgemm_f32) and csrc/simple_attn.hip (dif_simple_apply_f32): a kernel per translation
 // unit (anonymous namespace), one source.
 #pragma once
-#include "dif_common.h"
+#include "split_bf16.h"
 
 namespace {
 
 using dif::f32x4;
+using dif::bf16x8, dif::split8;
 
 // ---- row-GEMM at one head of 65..128 x 65..128 on split-bfloat16 operands (round 5: training at hidden 128) -------------
 // rowgemm_wide_kernel multiplies on the fp32 matrix core and gives each 64 output columns their own workgroup: A is read once
@@ -15,8 +16,6 @@ using dif::f32x4;
 // 128 x 128) and the rows split into hi + lo as they arrive: three v_mfma_f32_16x16x32_bf16 per (feature tile, 32 channels),
 // 96 instructions of 16 cycles per 16 rows instead of 256 of 32.  The dropped lo.lo term is 2^-16 of a product (~4e-6 of the
 // result; the gradients are held to 1e-4).  DIFFORMER_EXACT_FP32=1 keeps the fp32 kernel.
-typedef __bf16 rg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 rg_bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int kRsWaves = 8;
 
 __global__ __launch_bounds__(64 * kRsWaves) void rowgemm_split_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Mat,
@@ -27,7 +26,7 @@ __global__ __launch_bounds__(64 * kRsWaves) void rowgemm_split_kernel(const floa
                                                                       float* __restrict__ out, int64_t ldo,
                                                                       const float* __restrict__ norm2, const float* __restrict__ den_vec,
                                                                       float den_add) {
-    extern __shared__ __attribute__((aligned(16))) rg_bf16x8 sm_frag[];          // [hi | lo][ft < 8][kb < 4][lane]
+    extern __shared__ __attribute__((aligned(16))) bf16x8 sm_frag[];          // [hi | lo][ft < 8][kb < 4][lane]
     __shared__ __attribute__((aligned(16))) float sm_bias[128], sm_u[128], sm_den[128];   // per-column / per-channel epilogue operands (zero when absent)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, lg = lane >> 4;
@@ -44,6 +43,9 @@ __global__ __launch_bounds__(64 * kRsWaves) void rowgemm_split_kernel(const floa
         const int ln = e & 63, kb = (e >> 6) & 3, ft = e >> 8;
         const int c = 16 * ft + (ln & 15), k0 = 32 * kb + 4 * (ln >> 4);
         // (eight raw loads from clamped indices in flight, masked afterwards: guarded, each was a serialised round trip)
+        // rowgemm_wide_split_kernel (csrc/simple_attn_bwd.hip) stages its slab with this same loop body and other fragment
+        // indices.  It stays written out in both: moved into a shared function (load, mask and scale, split), even the mask
+        // alone, both kernels compile to different code (the compiler vectorises the scaling differently).  The split is shared.
         f32x4 w0, w1;
         const int cc = c < C ? c : C - 1;
 #pragma unroll
@@ -57,11 +59,7 @@ __global__ __launch_bounds__(64 * kRsWaves) void rowgemm_split_kernel(const floa
             w0[t] = (c < C && k0 + t < K) ? mat_scale * w0[t] : 0.f;
             w1[t] = (c < C && k0 + 16 + t < K) ? mat_scale * w1[t] : 0.f;
         }
-        const rg_bf16x4 h0 = __builtin_convertvector(w0, rg_bf16x4), h1 = __builtin_convertvector(w1, rg_bf16x4);
-        const rg_bf16x4 l0 = __builtin_convertvector(w0 - __builtin_convertvector(h0, f32x4), rg_bf16x4);
-        const rg_bf16x4 l1 = __builtin_convertvector(w1 - __builtin_convertvector(h1, f32x4), rg_bf16x4);
-        sm_frag[e] = rg_bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        sm_frag[8 * 4 * 64 + e] = rg_bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+        split8(w0, w1, sm_frag[e], sm_frag[8 * 4 * 64 + e]);
     }
     __syncthreads();
     const float beta = (Cin && beta_dev) ? *beta_dev : 1.0f;
@@ -87,7 +85,7 @@ __global__ __launch_bounds__(64 * kRsWaves) void rowgemm_split_kernel(const floa
         const int64_t row = st * 16 + l15;
         const bool row_ok = row < n_rows;
         const int64_t rowc = row_ok ? row : n_rows - 1;
-        rg_bf16x8 xh[4], xl[4];
+        bf16x8 xh[4], xl[4];
         float dpart = 0.f;
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
@@ -99,11 +97,7 @@ __global__ __launch_bounds__(64 * kRsWaves) void rowgemm_split_kernel(const floa
 #pragma unroll
                 for (int t = 0; t < 4; ++t) dpart += a0[t] * d0[t] + a1[t] * d1[t];
             }
-            const rg_bf16x4 h0 = __builtin_convertvector(a0, rg_bf16x4), h1 = __builtin_convertvector(a1, rg_bf16x4);
-            const rg_bf16x4 l0 = __builtin_convertvector(a0 - __builtin_convertvector(h0, f32x4), rg_bf16x4);
-            const rg_bf16x4 l1 = __builtin_convertvector(a1 - __builtin_convertvector(h1, f32x4), rg_bf16x4);
-            xh[kb] = rg_bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-            xl[kb] = rg_bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+            split8(a0, a1, xh[kb], xl[kb]);
         }
         load_a(an, st + stride < n_steps ? st + stride : st);               // the next rows arrive under this tile's products
         f32x4 cin[8];
@@ -125,8 +119,9 @@ __global__ __launch_bounds__(64 * kRsWaves) void rowgemm_split_kernel(const floa
         for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
             for (int ft = 0; ft < 8; ++ft) {
-                const rg_bf16x8 wh = sm_frag[(ft * 4 + kb) * 64 + lane], wl = sm_frag[8 * 4 * 64 + (ft * 4 + kb) * 64 + lane];
-                acc[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[kb], acc[ft], 0, 0, 0);      // small terms first
+                const bf16x8 wh = sm_frag[(ft * 4 + kb) * 64 + lane], wl = sm_frag[8 * 4 * 64 + (ft * 4 + kb) * 64 + lane];
+                // small terms first, hi.lo ahead of lo.hi (not dif::mfma3's order)
+                acc[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[kb], acc[ft], 0, 0, 0);
                 acc[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh[kb], acc[ft], 0, 0, 0);
                 acc[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh[kb], acc[ft], 0, 0, 0);
             }

@@ -20,12 +20,11 @@
 namespace {
 
 using dif::f32x4;
+using dif::zero4;
 
 constexpr int kB = 80;                 // padded matrix extent: 64 + the augmented index + padding to 5 MFMA tiles
 constexpr int kAug = 64;               // index of the augmented row / column
 constexpr int kBgChunksMax = 512;
-
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
 // ---- Gram partials: one wave = one workgroup = one partial record [G: C x C][sx: C] ------------------------
 __global__ __launch_bounds__(64) void gram_bg_kernel(const float* __restrict__ x, int64_t ldx, int64_t n_rows, int C,

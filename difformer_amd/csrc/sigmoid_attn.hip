@@ -12,70 +12,18 @@
 //                                  register the lane already holds (B operand = P[reg]).
 // Compute-bound on the f32 matrix pipe: 4*N*L*H*D FLOP.
 #include <type_traits>
-#include "dif_common.h"
+#include "split_bf16.h"
 #include "sigmoid_wide.h"
 
 namespace {
 
 using dif::f32x4;
+using dif::bf16x8, dif::ld4, dif::ld4_raw, dif::mask4, dif::mfma3, dif::sigmoid_hw, dif::split8;
 
 constexpr int kWaves = 8;     // waves per workgroup; each takes every 8th 16-key tile of the workgroup's key range
 constexpr int kQT = 2;        // 16-query tiles per wave: every K / V fragment fetched from L2 feeds 2x the MFMAs
 constexpr int kQGroup = 16 * kQT;   // queries per workgroup
 constexpr int kDTile = 64;    // output columns per workgroup (grid.y covers heads x ceil(D/64))
-
-// Branch-free fragment load: out-of-range rows / columns are read from a clamped (valid) address and
-// zeroed afterwards, so the compiler can issue all of a tile's loads back to back (a guarded load is
-// its own exec-masked branch region and serialises).
-template <bool VEC, typename T>
-__device__ __forceinline__ f32x4 ld4(const T* __restrict__ base, int64_t ld, int64_t rc, bool rok,
-                                     int col0, int c, int width) {
-    f32x4 z;
-    if (VEC) {
-        const bool cok = c < width;                       // width % 4 == 0 here
-        z = dif::Elem<T>::ld4(base + rc * ld + col0 + (cok ? c : 0));
-        if (!(rok && cok)) z = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool cok = c + i < width;
-            const float t = dif::Elem<T>::ld(base + rc * ld + col0 + (cok ? c + i : 0));
-            z[i] = (rok && cok) ? t : 0.f;
-        }
-    }
-    return z;
-}
-
-// The two halves of ld4 for software-pipelined loads: the raw (clamped-address) load is issued a step ahead and NOT touched until
-// the step that uses it -- masking at load time would make the issuing step wait for the data.
-template <bool VEC, typename T>
-__device__ __forceinline__ f32x4 ld4_raw(const T* __restrict__ base, int64_t ld, int64_t rc, int col0, int c, int width) {
-    f32x4 z;
-    if (VEC) {
-        z = dif::Elem<T>::ld4(base + rc * ld + col0 + (c < width ? c : 0));
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) z[i] = dif::Elem<T>::ld(base + rc * ld + col0 + (c + i < width ? c + i : 0));
-    }
-    return z;
-}
-template <bool VEC>
-__device__ __forceinline__ f32x4 mask4(f32x4 z, bool rok, int c, int width) {
-    if (VEC) {
-        if (!(rok && c < width)) z = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (!(rok && c + i < width)) z[i] = 0.f;
-    }
-    return z;
-}
-
-// sigma(x) with the hardware exp2 / rcp (each ~1 ulp): far inside the 1e-4 parity budget, and ~5x
-// fewer VALU instructions than expf + IEEE division next to the MFMAs.
-__device__ __forceinline__ float sigmoidf(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
-}
 
 // grid: (ceil(N/32), H * ceil(D/64), S key splits); block 512.
 // S == 1: writes the normalised output.  S > 1 (small N: not enough query groups to fill 256 CUs): writes
@@ -93,15 +41,6 @@ __device__ __forceinline__ float sigmoidf(float x) {
 // peak.  The wave takes TWO 16-key tiles per step: the second contraction runs 32 keys deep, and its B operand is still the
 // lane's own registers -- k-slot 8 lg + s <-> key 4 lg + s of the first tile (s < 4) / of the second (s >= 4), the same map on
 // the V side.  Scores ~4e-6 |q||k|, sigma is 1/4-Lipschitz.  DIFFORMER_EXACT_FP32=1 keeps the fp32 chain.
-typedef __bf16 sg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 sg_bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void sg_split8(const f32x4& a, const f32x4& b, sg_bf16x8& hi, sg_bf16x8& lo) {
-    const sg_bf16x4 h0 = __builtin_convertvector(a, sg_bf16x4), h1 = __builtin_convertvector(b, sg_bf16x4);
-    const sg_bf16x4 l0 = __builtin_convertvector(a - __builtin_convertvector(h0, f32x4), sg_bf16x4);
-    const sg_bf16x4 l1 = __builtin_convertvector(b - __builtin_convertvector(h1, f32x4), sg_bf16x4);
-    hi = sg_bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-    lo = sg_bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-}
 
 template <bool VEC, bool QREG, bool SEG, typename T = float, bool SPLIT = false>
 __global__ __launch_bounds__(512) void sigmoid_attn_kernel(const T* __restrict__ q, int64_t ldq,
@@ -168,11 +107,11 @@ __global__ __launch_bounds__(512) void sigmoid_attn_kernel(const T* __restrict__
     const int64_t kt1 = (kt0 + per < n_ktiles) ? kt0 + per : n_ktiles;
     if constexpr (SPLIT) {
         static_assert(QREG, "split-bf16 sigmoid attention keeps the query fragments in registers (M <= 64)");
-        sg_bf16x8 qh[kQT][2], ql[kQT][2];
+        bf16x8 qh[kQT][2], ql[kQT][2];
 #pragma unroll
         for (int t = 0; t < kQT; ++t)
 #pragma unroll
-            for (int kb = 0; kb < 2; ++kb) sg_split8(qv[t][2 * kb], qv[t][2 * kb + 1], qh[t][kb], ql[t][kb]);
+            for (int kb = 0; kb < 2; ++kb) split8(qv[t][2 * kb], qv[t][2 * kb + 1], qh[t][kb], ql[t][kb]);
         const int64_t key_limit = (kt1 * 16 < L) ? kt1 * 16 : L;         // the keys of THIS workgroup's range end here
         // The K and V fragments of the NEXT step are in flight under this step's products (64 VGPRs): a step is a chain
         // loads -> products -> sigma -> products, and one workgroup per CU leaves two waves per SIMD to hide it.  Raw loads
@@ -201,7 +140,7 @@ __global__ __launch_bounds__(512) void sigmoid_attn_kernel(const T* __restrict__
         for (int64_t kt = kt0 + 2 * wave; kt < kt1; kt += 2 * kWaves) {
             const int64_t kbase = kt * 16;
             f32x4 kc[2][4];
-            sg_bf16x8 vh[4], vl[4];
+            bf16x8 vh[4], vl[4];
 #pragma unroll
             for (int tile = 0; tile < 2; ++tile)
 #pragma unroll
@@ -215,7 +154,7 @@ __global__ __launch_bounds__(512) void sigmoid_attn_kernel(const T* __restrict__
 #pragma unroll
                     for (int reg = 0; reg < 4; ++reg)
                         va[tile][reg] = (dok && kbase + 16 * tile + 4 * lg + reg < key_limit) ? vn[dtl][tile][reg] : 0.f;
-                sg_split8(va[0], va[1], vh[dtl], vl[dtl]);
+                split8(va[0], va[1], vh[dtl], vl[dtl]);
             }
             {
                 const int64_t nxt = kt + 2 * kWaves;
@@ -230,18 +169,16 @@ __global__ __launch_bounds__(512) void sigmoid_attn_kernel(const T* __restrict__
                 for (int t = 0; t < kQT; ++t) s2[tile][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb) {
-                    sg_bf16x8 kh, kl;
-                    sg_split8(kx[2 * kb], kx[2 * kb + 1], kh, kl);
+                    bf16x8 kh, kl;
+                    split8(kx[2 * kb], kx[2 * kb + 1], kh, kl);
 #pragma unroll
                     for (int t = 0; t < kQT; ++t) {
-                        s2[tile][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh[t][kb], s2[tile][t], 0, 0, 0);      // small terms first
-                        s2[tile][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql[t][kb], s2[tile][t], 0, 0, 0);
-                        s2[tile][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, qh[t][kb], s2[tile][t], 0, 0, 0);
+                        s2[tile][t] = mfma3(kh, kl, qh[t][kb], ql[t][kb], s2[tile][t]);
                     }
                 }
             }
             // P = sigma(S) masked beyond the range (difformer.py:47), its row sums (:50-51), split for the second contraction
-            sg_bf16x8 ph[kQT], pl[kQT];
+            bf16x8 ph[kQT], pl[kQT];
 #pragma unroll
             for (int t = 0; t < kQT; ++t) {
                 f32x4 pp[2];
@@ -249,15 +186,16 @@ __global__ __launch_bounds__(512) void sigmoid_attn_kernel(const T* __restrict__
                 for (int tile = 0; tile < 2; ++tile)
 #pragma unroll
                     for (int reg = 0; reg < 4; ++reg) {
-                        pp[tile][reg] = (kbase + 16 * tile + 4 * lg + reg < key_limit) ? sigmoidf(s2[tile][t][reg]) : 0.f;
+                        pp[tile][reg] = (kbase + 16 * tile + 4 * lg + reg < key_limit) ? sigmoid_hw(s2[tile][t][reg]) : 0.f;
                         den[t] += pp[tile][reg];
                     }
-                sg_split8(pp[0], pp[1], ph[t], pl[t]);
+                split8(pp[0], pp[1], ph[t], pl[t]);
             }
 #pragma unroll
             for (int dtl = 0; dtl < 4; ++dtl)
 #pragma unroll
                 for (int t = 0; t < kQT; ++t) {
+                    // dif::mfma3's order, written out: through the helper this loop compiles to a different schedule
                     acc_o[t][dtl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vl[dtl], ph[t], acc_o[t][dtl], 0, 0, 0);
                     acc_o[t][dtl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh[dtl], pl[t], acc_o[t][dtl], 0, 0, 0);
                     acc_o[t][dtl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh[dtl], ph[t], acc_o[t][dtl], 0, 0, 0);
@@ -312,7 +250,7 @@ __global__ __launch_bounds__(512) void sigmoid_attn_kernel(const T* __restrict__
         for (int t = 0; t < kQT; ++t)
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
-                p[t][reg] = (kbase + 4 * lg + reg < L) ? sigmoidf(s[t][reg]) : 0.f;
+                p[t][reg] = (kbase + 4 * lg + reg < L) ? sigmoid_hw(s[t][reg]) : 0.f;
                 den[t] += p[t][reg];                                      // :50-51 row sum
             }
 #pragma unroll

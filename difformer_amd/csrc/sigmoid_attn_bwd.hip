@@ -16,65 +16,18 @@
 // Covers M, D <= 64 (one fragment set per side); wider heads re-derive the gradient with tensor ops on the host side.
 // FLOPs: 14 N L H D against the forward's 4 N L H D.
 #include <stdlib.h>
-#include "dif_common.h"
+#include "split_bf16.h"
 #include "sigmoid_wide.h"
 
 namespace {
 
 using dif::f32x4;
+using dif::bf16x8, dif::ld4, dif::ld4_raw, dif::mask4, dif::mfma3, dif::sigmoid_hw, dif::split8;
 
 constexpr int kWaves = 8;
 constexpr int kXT = 2;                  // 16-row tiles of the stationary side per workgroup
 constexpr int kXGroup = 16 * kXT;
 constexpr int kCols = 64;               // M, D <= 64
-
-template <bool VEC>
-__device__ __forceinline__ f32x4 ld4(const float* __restrict__ base, int64_t ld, int64_t rc, bool rok, int col0, int c,
-                                     int width) {
-    f32x4 z;
-    if (VEC) {
-        const bool cok = c < width;
-        z = *reinterpret_cast<const f32x4*>(base + rc * ld + col0 + (cok ? c : 0));
-        if (!(rok && cok)) z = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool cok = c + i < width;
-            const float t = base[rc * ld + col0 + (cok ? c + i : 0)];
-            z[i] = (rok && cok) ? t : 0.f;
-        }
-    }
-    return z;
-}
-
-// The two halves of ld4 for software-pipelined loads: the raw (clamped-address) load is issued a step ahead and NOT touched until
-// the step that uses it -- a mask (or a branch) at issue time makes the issuing step wait for the data.
-template <bool VEC>
-__device__ __forceinline__ f32x4 ld4_raw(const float* __restrict__ base, int64_t ld, int64_t rc, int col0, int c, int width) {
-    f32x4 z;
-    if (VEC) {
-        z = *reinterpret_cast<const f32x4*>(base + rc * ld + col0 + (c < width ? c : 0));
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) z[i] = base[rc * ld + col0 + (c + i < width ? c + i : 0)];
-    }
-    return z;
-}
-template <bool VEC>
-__device__ __forceinline__ f32x4 mask4(f32x4 z, bool rok, int c, int width) {
-    if (VEC) {
-        if (!(rok && c < width)) z = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (!(rok && c + i < width)) z[i] = 0.f;
-    }
-    return z;
-}
-
-__device__ __forceinline__ float sigmoidf(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
-}
 
 // cinv[n,h] = 1 / den[n,h], delta[n,h] = g[n,h,:] . out[n,h,:]
 __global__ __launch_bounds__(256) void sigmoid_bwd_prep_kernel(const float* __restrict__ g, int64_t ldg,
@@ -113,20 +66,6 @@ __global__ __launch_bounds__(256) void sigmoid_bwd_prep_kernel(const float* __re
 // step so that the second contractions run 32 swept rows deep; their B operand is still the lane's own registers: k-slot
 // 8 lg + e <-> swept row 4 lg + e of the first tile (e < 4) / 4 lg + e - 4 of the second -- the forward kernel's map.
 // Gradients move by a few 1e-6 relative; DIFFORMER_EXACT_FP32=1 / dif_set_exact_fp32 keeps the fp32 chain.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
-    const bf16x4 h0 = __builtin_convertvector(a, bf16x4), h1 = __builtin_convertvector(b, bf16x4);
-    const bf16x4 l0 = __builtin_convertvector(a - __builtin_convertvector(h0, f32x4), bf16x4);
-    const bf16x4 l1 = __builtin_convertvector(b - __builtin_convertvector(h1, f32x4), bf16x4);
-    hi = bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-    lo = bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-}
-__device__ __forceinline__ f32x4 mfma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);          // small terms first
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
-}
 
 template <int MODE, bool VEC, bool SEG = false, bool SPLIT = false>
 __global__ __launch_bounds__(512) void sigmoid_bwd_kernel(const float* __restrict__ x1, int64_t ldx1,
@@ -262,7 +201,7 @@ __global__ __launch_bounds__(512) void sigmoid_bwd_kernel(const float* __restric
                 for (int tile = 0; tile < 2; ++tile)
 #pragma unroll
                     for (int reg = 0; reg < 4; ++reg) {
-                        const float p = zok[tile][reg] ? sigmoidf(s[tile][t][reg]) : 0.f;
+                        const float p = zok[tile][reg] ? sigmoid_hw(s[tile][t][reg]) : 0.f;
                         const float c = (MODE == 0) ? cx[t] : cy[tile][reg];
                         const float dl = (MODE == 0) ? dx[t] : dy[tile][reg];
                         pc[tile][reg] = p * c;
@@ -390,7 +329,7 @@ __global__ __launch_bounds__(512) void sigmoid_bwd_kernel(const float* __restric
 #pragma unroll
                 for (int reg = 0; reg < 4; ++reg) {
                     const bool ok = ybase + 4 * lg + reg < Y;
-                    const float p = ok ? sigmoidf(s[t][reg]) : 0.f;
+                    const float p = ok ? sigmoid_hw(s[t][reg]) : 0.f;
                     const float c = (MODE == 0) ? cx[t] : (ok ? cyn[reg] : 0.f);      // per-query scalars ride with the swept row
                     const float dl = (MODE == 0) ? dx[t] : (ok ? dyn[reg] : 0.f);
                     pc[t][reg] = p * c;

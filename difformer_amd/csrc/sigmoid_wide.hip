@@ -30,20 +30,15 @@
 // The stream is cut into S splits when there are fewer than 256 workgroups' worth of stationary rows (15,000 rows = 118
 // workgroups of 8 waves); partial sums are added in split order (bitwise reproducible).
 #include <type_traits>
-#include "dif_common.h"
+#include "split_bf16.h"
 #include "sigmoid_wide.h"
 
 namespace {
 
 using dif::f32x4;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using dif::bf16x8, dif::sigmoid_hw, dif::split_planes;
 
 constexpr int kMaxKS = 16;                      // 512 columns
-
-__device__ __forceinline__ float sigmoidf(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
-}
 
 // product terms (streamed plane a, stationary plane b) and the accumulator each adds to (0 = hi.hi, 1 = the small terms):
 // consecutive terms alternate accumulators, so that no MFMA waits for the one before it
@@ -54,20 +49,6 @@ template <> struct Terms<2> {
     static __device__ __forceinline__ constexpr int b(int i) { return i == 2 ? 1 : 0; }
     static __device__ __forceinline__ constexpr int acc(int i) { return i == 1 ? 0 : 1; }
 };
-
-// x -> NP bf16 planes (round to nearest even; plane p + 1 holds what plane p left)
-template <int NP>
-__device__ __forceinline__ void split_planes(f32x4 x0, f32x4 x1, bf16x8 (&pl)[NP]) {
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const bf16x4 h0 = __builtin_convertvector(x0, bf16x4), h1 = __builtin_convertvector(x1, bf16x4);
-        pl[p] = bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        if (p + 1 < NP) {
-            x0 -= __builtin_convertvector(h0, f32x4);
-            x1 -= __builtin_convertvector(h1, f32x4);
-        }
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------------------------
 // pack: one workgroup per (32-row tile, head, chunk of 64 columns = 2 column steps / 4 column tiles); one fragment lane per
@@ -412,7 +393,7 @@ __global__ __launch_bounds__(64 * W) void sigw_fwd_kernel(FwdArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const bool ok = 32ll * t + 16 * rt + 4 * lg + r < a.NY;      // padded rows of the stream: sigma(0) = 1/2 stays out of den
-                    p[rt][r] = ok ? sigmoidf(s[qt][rt][r]) : 0.f;
+                    p[rt][r] = ok ? sigmoid_hw(s[qt][rt][r]) : 0.f;
                     den[qt] += p[rt][r];
                 }
             split_planes<NP>(p[0], p[1], pb[qt]);
@@ -486,7 +467,7 @@ __global__ __launch_bounds__(64 * W) void sigw_bwd_kernel(BwdArgs a) {
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float pp = sigmoidf(s[0][rt][r]);
+                const float pp = sigmoid_hw(s[0][rt][r]);
                 ds[rt][r] = (tt[0][rt][r] - dv[rt][r]) * (pp - pp * pp);
             }
         bf16x8 pb[1][NP];

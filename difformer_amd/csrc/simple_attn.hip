@@ -630,13 +630,12 @@ int simple_apply_entry(const T* q, int64_t ldq, const float* reduced, int64_t n_
 // simple_reduce_kernel<sym> writes, so record_finalize_kernel sums them unchanged.  DIFFORMER_EXACT_FP32=1 keeps the fp32 pass.
 // ------------------------------------------------------------------------------------------------------------------
 namespace {
-typedef __bf16 gs_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gs_bf16x4 __attribute__((ext_vector_type(4)));
+using dif::bf16x4, dif::bf16x8, dif::split_bf16;
 constexpr int kSlabMaxMT = 5;
 
 __global__ __launch_bounds__(512) void gram_slab_kernel(const float* __restrict__ x, int64_t ldx, int64_t n_rows, int C, int MT,
                                                         float* __restrict__ ws, int64_t ws_stride) {
-    __shared__ __attribute__((aligned(16))) gs_bf16x8 sm_op[2 * kSlabMaxMT * 4 * 64];      // [hi | lo][block][t][lane]: 40 KiB
+    __shared__ __attribute__((aligned(16))) bf16x8 sm_op[2 * kSlabMaxMT * 4 * 64];      // [hi | lo][block][t][lane]: 40 KiB
     __shared__ float sm_sx[4][kSlabMaxMT * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, lg = lane >> 4;
@@ -681,19 +680,17 @@ __global__ __launch_bounds__(512) void gram_slab_kernel(const float* __restrict_
     for (int64_t slab = first; slab < n_slabs; slab += stride) {
         // ---- registers -> LDS operands ----
         if (stager) {
-            gs_bf16x4 h[8], l[8];
+            bf16x4 h[8], l[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 sx += nxt[j];
-                h[j] = __builtin_convertvector(nxt[j], gs_bf16x4);
-                const f32x4 back = __builtin_convertvector(h[j], f32x4);
-                l[j] = __builtin_convertvector(nxt[j] - back, gs_bf16x4);
+                split_bf16(nxt[j], h[j], l[j]);
             }
             const int b = cq >> 4, ln = 16 * slg + (cq & 15);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                sm_op[((0 * kSlabMaxMT + b) * 4 + t) * 64 + ln] = gs_bf16x8{h[0][t], h[1][t], h[2][t], h[3][t], h[4][t], h[5][t], h[6][t], h[7][t]};
-                sm_op[((1 * kSlabMaxMT + b) * 4 + t) * 64 + ln] = gs_bf16x8{l[0][t], l[1][t], l[2][t], l[3][t], l[4][t], l[5][t], l[6][t], l[7][t]};
+                sm_op[((0 * kSlabMaxMT + b) * 4 + t) * 64 + ln] = bf16x8{h[0][t], h[1][t], h[2][t], h[3][t], h[4][t], h[5][t], h[6][t], h[7][t]};
+                sm_op[((1 * kSlabMaxMT + b) * 4 + t) * 64 + ln] = bf16x8{l[0][t], l[1][t], l[2][t], l[3][t], l[4][t], l[5][t], l[6][t], l[7][t]};
             }
         }
         __syncthreads();
@@ -702,7 +699,7 @@ __global__ __launch_bounds__(512) void gram_slab_kernel(const float* __restrict_
         for (int k = 0; k < kTilesPerWave; ++k) {
             if (tix[k] >= NT) continue;
             const int mt = mts[k], dt = dts[k];
-            gs_bf16x8 bh[4], bl[4];
+            bf16x8 bh[4], bl[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 bh[u] = sm_op[((0 * kSlabMaxMT + dt) * 4 + u) * 64 + lane];
@@ -710,11 +707,12 @@ __global__ __launch_bounds__(512) void gram_slab_kernel(const float* __restrict_
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const gs_bf16x8 ah = sm_op[((0 * kSlabMaxMT + mt) * 4 + t) * 64 + lane];
-                const gs_bf16x8 al = sm_op[((1 * kSlabMaxMT + mt) * 4 + t) * 64 + lane];
+                const bf16x8 ah = sm_op[((0 * kSlabMaxMT + mt) * 4 + t) * 64 + lane];
+                const bf16x8 al = sm_op[((1 * kSlabMaxMT + mt) * 4 + t) * 64 + lane];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    acc[k][t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[u], acc[k][t][u], 0, 0, 0);      // small terms first
+                    // small terms first, hi.lo ahead of lo.hi (not dif::mfma3's order)
+                    acc[k][t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[u], acc[k][t][u], 0, 0, 0);
                     acc[k][t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[u], acc[k][t][u], 0, 0, 0);
                     acc[k][t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[u], acc[k][t][u], 0, 0, 0);
                 }
@@ -757,7 +755,7 @@ namespace {
 __global__ __launch_bounds__(256, 2) void reduce_slab_kernel(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k,
                                                           int64_t ldk, const float* __restrict__ v, int64_t ldv, int64_t n_rows,
                                                           int M, int D, float* __restrict__ ws, int64_t ws_stride, int t_main) {
-    __shared__ __attribute__((aligned(16))) gs_bf16x8 sm_k[2 * 2 * 4 * 64], sm_v[2 * 2 * 4 * 64];      // [hi | lo][block][t][lane]
+    __shared__ __attribute__((aligned(16))) bf16x8 sm_k[2 * 2 * 4 * 64], sm_v[2 * 2 * 4 * 64];      // [hi | lo][block][t][lane]
     __shared__ float sm_sx[2][4][128];
     __shared__ float sm_sq[2][128];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -803,30 +801,28 @@ __global__ __launch_bounds__(256, 2) void reduce_slab_kernel(const float* __rest
     if (first < n_slabs) fetch(first);
     for (int64_t slab = first; slab < n_slabs; slab += stride) {
         if (stager) {
-            gs_bf16x4 h[8], l[8];
+            bf16x4 h[8], l[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 sx += nxt[j];
                 sq += nxt[j][0] * nxt[j][0] + nxt[j][1] * nxt[j][1] + nxt[j][2] * nxt[j][2] + nxt[j][3] * nxt[j][3];
                 if (with_q) sqq += nxq[j][0] * nxq[j][0] + nxq[j][1] * nxq[j][1] + nxq[j][2] * nxq[j][2] + nxq[j][3] * nxq[j][3];
-                h[j] = __builtin_convertvector(nxt[j], gs_bf16x4);
-                const f32x4 back = __builtin_convertvector(h[j], f32x4);
-                l[j] = __builtin_convertvector(nxt[j] - back, gs_bf16x4);
+                split_bf16(nxt[j], h[j], l[j]);
             }
             {
-                gs_bf16x8* op = role == 0 ? sm_k : sm_v;
+                bf16x8* op = role == 0 ? sm_k : sm_v;
                 const int b = cq >> 4, ln = 16 * slg + (cq & 15);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    op[((0 * 2 + b) * 4 + t) * 64 + ln] = gs_bf16x8{h[0][t], h[1][t], h[2][t], h[3][t], h[4][t], h[5][t], h[6][t], h[7][t]};
-                    op[((1 * 2 + b) * 4 + t) * 64 + ln] = gs_bf16x8{l[0][t], l[1][t], l[2][t], l[3][t], l[4][t], l[5][t], l[6][t], l[7][t]};
+                    op[((0 * 2 + b) * 4 + t) * 64 + ln] = bf16x8{h[0][t], h[1][t], h[2][t], h[3][t], h[4][t], h[5][t], h[6][t], h[7][t]};
+                    op[((1 * 2 + b) * 4 + t) * 64 + ln] = bf16x8{l[0][t], l[1][t], l[2][t], l[3][t], l[4][t], l[5][t], l[6][t], l[7][t]};
                 }
             }
         }
         __syncthreads();
         if (slab + stride < n_slabs) fetch(slab + stride);
         if (worker) {
-            gs_bf16x8 bh[4], bl[4];
+            bf16x8 bh[4], bl[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 bh[u] = sm_v[((0 * 2 + dt) * 4 + u) * 64 + lane];
@@ -834,10 +830,11 @@ __global__ __launch_bounds__(256, 2) void reduce_slab_kernel(const float* __rest
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const gs_bf16x8 ah = sm_k[((0 * 2 + mt) * 4 + t) * 64 + lane];
-                const gs_bf16x8 al = sm_k[((1 * 2 + mt) * 4 + t) * 64 + lane];
+                const bf16x8 ah = sm_k[((0 * 2 + mt) * 4 + t) * 64 + lane];
+                const bf16x8 al = sm_k[((1 * 2 + mt) * 4 + t) * 64 + lane];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
+                    // small terms first, hi.lo ahead of lo.hi (not dif::mfma3's order)
                     acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[u], acc[t][u], 0, 0, 0);
                     acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[u], acc[t][u], 0, 0, 0);
                     acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[u], acc[t][u], 0, 0, 0);

@@ -379,9 +379,6 @@ __global__ __launch_bounds__(64 * kRgWaves) void rowgemm_wide_kernel(const float
 // v_mfma_f32_16x16x32_bf16 per (feature tile, 32 channels) = 24 instructions of 16 cycles per 64 channels.  The dropped lo.lo
 // term is 2^-16 of a product (~4e-6 of the result; the gradients are held to 1e-4); DIFFORMER_EXACT_FP32=1 keeps the fp32 kernel.
 // K <= 512 and K, C multiples of 4 with 16-byte aligned rows (the launcher checks); LDS: 16 KiB per 64 channels.
-typedef __bf16 rw_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 rw_bf16x4 __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(64 * kRgWaves) void rowgemm_wide_split_kernel(const float* __restrict__ A, int64_t lda, int a_head_stride,
                                                                            const float* __restrict__ Mat, int ldm, int mat_head_stride,
                                                                            int mat_t, float mat_scale, const float* __restrict__ bias,
@@ -390,14 +387,14 @@ __global__ __launch_bounds__(64 * kRgWaves) void rowgemm_wide_split_kernel(const
                                                                            const float* __restrict__ Cin, int64_t ldc,
                                                                            const float* __restrict__ beta_dev, int64_t n_rows, int K,
                                                                            int C, float* __restrict__ out, int64_t ldo) {
-    extern __shared__ __attribute__((aligned(16))) rw_bf16x8 sm_wfrag[];      // [hi | lo][ft < 4][kb < KB][lane]
+    extern __shared__ __attribute__((aligned(16))) bf16x8 sm_wfrag[];      // [hi | lo][ft < 4][kb < KB][lane]
     const int h = blockIdx.z, ct = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, lg = lane >> 4;
     const int KT = (K + 63) >> 6, KB = 2 * KT;
     const float* mat = Mat + static_cast<int64_t>(h) * mat_head_stride;
     const int n_frag = 4 * KB * 64;
-    for (int e = threadIdx.x; e < n_frag; e += 64 * kRgWaves) {
+    for (int e = threadIdx.x; e < n_frag; e += 64 * kRgWaves) {       // rowgemm_split_kernel's staging loop: see there why it is written out twice
         const int ln = e & 63, kb = (e >> 6) % KB, ft = (e >> 6) / KB;
         const int c = ct * 64 + 16 * ft + (ln & 15), k0 = 32 * kb + 4 * (ln >> 4);
         const int cc = c < C ? c : C - 1;
@@ -413,11 +410,7 @@ __global__ __launch_bounds__(64 * kRgWaves) void rowgemm_wide_split_kernel(const
             w0[t] = (c < C && k0 + t < K) ? mat_scale * w0[t] : 0.f;
             w1[t] = (c < C && k0 + 16 + t < K) ? mat_scale * w1[t] : 0.f;
         }
-        const rw_bf16x4 h0 = __builtin_convertvector(w0, rw_bf16x4), h1 = __builtin_convertvector(w1, rw_bf16x4);
-        const rw_bf16x4 l0 = __builtin_convertvector(w0 - __builtin_convertvector(h0, f32x4), rw_bf16x4);
-        const rw_bf16x4 l1 = __builtin_convertvector(w1 - __builtin_convertvector(h1, f32x4), rw_bf16x4);
-        sm_wfrag[e] = rw_bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        sm_wfrag[n_frag + e] = rw_bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+        split8(w0, w1, sm_wfrag[e], sm_wfrag[n_frag + e]);
     }
     __syncthreads();
 
@@ -444,17 +437,13 @@ __global__ __launch_bounds__(64 * kRgWaves) void rowgemm_wide_split_kernel(const
 #pragma unroll
         for (int t4 = 0; t4 < 4; ++t4) acc[t4] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int kt = 0; kt < KT; ++kt) {
-            rw_bf16x8 xh[2], xl[2];
+            bf16x8 xh[2], xl[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 f32x4 a0 = an[2 * j], a1 = an[2 * j + 1];
                 if (!(row_ok && kt * 64 + 32 * j + 4 * lg < K)) a0 = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (!(row_ok && kt * 64 + 32 * j + 16 + 4 * lg < K)) a1 = f32x4{0.f, 0.f, 0.f, 0.f};
-                const rw_bf16x4 h0 = __builtin_convertvector(a0, rw_bf16x4), h1 = __builtin_convertvector(a1, rw_bf16x4);
-                const rw_bf16x4 l0 = __builtin_convertvector(a0 - __builtin_convertvector(h0, f32x4), rw_bf16x4);
-                const rw_bf16x4 l1 = __builtin_convertvector(a1 - __builtin_convertvector(h1, f32x4), rw_bf16x4);
-                xh[j] = rw_bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                xl[j] = rw_bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+                split8(a0, a1, xh[j], xl[j]);
             }
             if (kt + 1 < KT) load_a(an, st, kt + 1);                           // the next channels / rows arrive under these products
             else load_a(an, st + stride < n_steps ? st + stride : st, 0);
@@ -463,8 +452,9 @@ __global__ __launch_bounds__(64 * kRgWaves) void rowgemm_wide_split_kernel(const
 #pragma unroll
                 for (int t4 = 0; t4 < 4; ++t4) {
                     const int at = (t4 * KB + 2 * kt + j) * 64 + lane;
-                    const rw_bf16x8 wh = sm_wfrag[at], wl = sm_wfrag[n_frag + at];
-                    acc[t4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[j], acc[t4], 0, 0, 0);      // small terms first
+                    const bf16x8 wh = sm_wfrag[at], wl = sm_wfrag[n_frag + at];
+                    // small terms first, hi.lo ahead of lo.hi (not dif::mfma3's order)
+                    acc[t4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[j], acc[t4], 0, 0, 0);
                     acc[t4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh[j], acc[t4], 0, 0, 0);
                     acc[t4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh[j], acc[t4], 0, 0, 0);
                 }

@@ -24,21 +24,10 @@
 namespace {
 
 using dif::f32x4;
+using dif::tile_product, dif::zero4;
 
 constexpr int kLd = 68;
 constexpr int kBlock = 64 * kLd;
-
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-
-// one 16 x 16 tile of a 64^3 product: lane holds D[16 ti + 4 lg + reg][16 tj + l15]
-template <typename FA, typename FB>
-__device__ __forceinline__ f32x4 tile_product(FA A, FB B, int ti, int tj, int l15, int lg) {
-    f32x4 d = zero4();
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks)
-        d = __builtin_amdgcn_mfma_f32_16x16x4f32(A(16 * ti + l15, 4 * ks + lg), B(4 * ks + lg, 16 * tj + l15), d, 0, 0, 0);
-    return d;
-}
 
 // 256 consecutive threads: out[o] = sum_i blk[o][i] v[i]  (COL = false)  or  sum_i blk[i][o] v[i]  (COL = true); four
 // lanes per output fold 16 terms each.  `t` = thread index inside the group of 256.

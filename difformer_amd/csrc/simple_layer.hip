@@ -17,11 +17,12 @@
 // out (and the slice-major copy) written once, against q, v, attn, conv written and re-read before.
 #include <type_traits>
 
-#include "dif_common.h"
+#include "split_bf16.h"
 
 namespace {
 
 using dif::f32x4;
+using dif::bf16x4, dif::bf16x8, dif::cat8, dif::dinv_of, dif::split_bf16, dif::tile_product, dif::zero4;
 using dif::Elem;
 
 constexpr int kWaves = 4;
@@ -30,13 +31,6 @@ constexpr int kWaves = 4;
 #endif
 constexpr int kHeadWaves = DIF_HEAD_WAVES;
 constexpr int kRecordChunksPerCU = 3;   // partial Gram records per CU that dif_gram_workspace_bytes makes room for
-
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-
-__device__ __forceinline__ float dinv_of(const int32_t* __restrict__ rowptr, int64_t row) {
-    const int32_t d = rowptr[row + 1] - rowptr[row];
-    return d > 0 ? sqrtf(1.0f / static_cast<float>(d)) : 0.f;
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // Gram record.  A wave reads four whole rows per instruction (lane = 16*lg + l15: row base + lg, columns 4*l15..+3), which
@@ -79,7 +73,6 @@ __global__ __launch_bounds__(64 * kGramWaves, 2) void gram_kernel(const T* __res
         // (k = 8 lg + u <-> row 4 u + lg: the same map on both sides of the product), packed by v_perm_b32.  The column sums
         // are one more product, against ones.  Float32-converted rows made this pass issue-bound at every size
         // (1,600,000 x 64: 131 us against 91 us for float32 rows, profiles/r05_experiments.md).
-        typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         auto load32 = [&](uint2 (&raw)[8], int64_t tile) {        // tile: index of a 32-row block
 #pragma unroll
@@ -89,7 +82,7 @@ __global__ __launch_bounds__(64 * kGramWaves, 2) void gram_kernel(const T* __res
             }
         };
         const int64_t n32 = (n_rows + 31) / 32;
-        const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
+        const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
         f32x4 accs[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) accs[t] = zero4();
@@ -100,7 +93,7 @@ __global__ __launch_bounds__(64 * kGramWaves, 2) void gram_kernel(const T* __res
 #pragma unroll
             for (int u = 0; u < 8; ++u) raw[u] = nraw[u];
             if (tile + stride < n32) load32(nraw, tile + stride);
-            bf16x8_t op[4];
+            bf16x8 op[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 u32x4 w;
@@ -110,7 +103,7 @@ __global__ __launch_bounds__(64 * kGramWaves, 2) void gram_kernel(const T* __res
                     // low halves (t even) or high halves (t odd) of the two dwords, row 2 j below row 2 j + 1
                     w[j] = __builtin_amdgcn_perm(a1, a0, (t & 1) ? 0x07060302u : 0x05040100u);
                 }
-                op[t] = __builtin_bit_cast(bf16x8_t, w);
+                op[t] = __builtin_bit_cast(bf16x8, w);
             }
             int a = 0;
 #pragma unroll
@@ -424,17 +417,6 @@ int gram_chunks(int64_t n_rows) {
 //   coef = [MnT: D x C (feature-major, a_s folded in)][cn: D][u: C][cd][s][|Q|^2][|K|^2]
 // ------------------------------------------------------------------------------------------------------------
 constexpr int kLd = 68;
-
-// one 16 x 16 tile of a 64 x 64 x 64 product on the fp32 MFMA: A(i, k), B(k, j) are LDS accessors;
-// lane holds D[16ti + 4lg + reg][16tj + l15]
-template <typename FA, typename FB>
-__device__ __forceinline__ f32x4 tile_product(FA A, FB B, int ti, int tj, int l15, int lg) {
-    f32x4 d = zero4();
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks)
-        d = __builtin_amdgcn_mfma_f32_16x16x4f32(A(16 * ti + l15, 4 * ks + lg), B(4 * ks + lg, 16 * tj + l15), d, 0, 0, 0);
-    return d;
-}
 
 // LDS of the coefficient stage (1024 threads): six padded 64 x 64 blocks and a few vectors
 struct CoefSmem {
@@ -781,16 +763,6 @@ __device__ __forceinline__ void gather_rows(f32x4 (&ga)[4], float& wsum, GatherC
 // v = hi + lo with hi = bf16(v), lo = bf16(v - hi); x.w ~ xl.wh + xh.wl + xh.wh on v_mfma_f32_16x16x32_bf16, which runs 16x
 // the fp32 matrix rate (the dropped xl.wl term is 2^-16 of the product: ~4e-6 on the logits).  The 64 -> 128-class product
 // was half of the kernel's 256 fp32 MFMAs per tile and the kernel was bound by them.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split_bf16(const f32x4& v, bf16x4& hi, bf16x4& lo) {
-    hi = __builtin_convertvector(v, bf16x4);
-    const f32x4 back = __builtin_convertvector(hi, f32x4);
-    lo = __builtin_convertvector(v - back, bf16x4);
-}
-__device__ __forceinline__ bf16x8 cat8(const bf16x4& a, const bf16x4& b) {
-    return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 
 // LDS layout of a 64 x 64 weight block for project_t: element (f, c) at [f/16][c/16][(c/4)%4][f%16][c%4].  The A fragment of
 // a lane (lg, l15) is then the 16 bytes at lg * 256 + l15 * 16 inside the (ft, cq) sub-block: the bank quad depends on l15
@@ -840,7 +812,8 @@ __device__ __forceinline__ void project_split(f32x4 (&y)[4], const f32x4 (&xa)[4
 #pragma unroll
         for (int ft = 0; ft < 4; ++ft) {
             const bf16x8 ah = wh[(ft * 2 + kb) * 64 + lane], al = wl[(ft * 2 + kb) * 64 + lane];
-            y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl[kb], y[ft], 0, 0, 0);      // small terms first
+            // small terms first, hi.lo ahead of lo.hi (not dif::mfma3's order)
+            y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xl[kb], y[ft], 0, 0, 0);
             y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, xh[kb], y[ft], 0, 0, 0);
             y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, xh[kb], y[ft], 0, 0, 0);
         }
@@ -1069,7 +1042,8 @@ void simple_layer_kernel(LayerArgsT<T> a) {
                     for (int ft = 0; ft < 4; ++ft) {
                         const int fr = (((blk * 4 + ft) * 2 + kb) << 6) + lane;
                         const bf16x8 wh = sm_wo[0][fr], wl = sm_wo[1][fr];
-                        z[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, ol[kb], z[ft], 0, 0, 0);      // small terms first
+                        // small terms first, hi.lo ahead of lo.hi (not dif::mfma3's order)
+                        z[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, ol[kb], z[ft], 0, 0, 0);
                         z[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, oh[kb], z[ft], 0, 0, 0);
                         z[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, oh[kb], z[ft], 0, 0, 0);
                     }

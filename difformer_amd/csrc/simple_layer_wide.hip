@@ -19,24 +19,12 @@
 //   operand is the x fragment already in registers, LayerNorm folds over the four lane groups, rows leave as 16-byte stores.
 // LDS: Mn^T and Wv as ready-made A fragments, [part hi | lo][h][ft][lane] x 16 bytes = 64 KiB each (one 16-wave workgroup per CU).
 #include <stdlib.h>
-#include "dif_common.h"
+#include "split_bf16.h"
 
 namespace {
 
 using dif::f32x4;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ void split_bf16(const f32x4& v, bf16x4& hi, bf16x4& lo) {
-    hi = __builtin_convertvector(v, bf16x4);
-    const f32x4 back = __builtin_convertvector(hi, f32x4);
-    lo = __builtin_convertvector(v - back, bf16x4);
-}
-__device__ __forceinline__ bf16x8 cat8(const bf16x4& a, const bf16x4& b) {
-    return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
+using dif::bf16x4, dif::bf16x8, dif::cat8, dif::split_bf16, dif::zero4;
 
 constexpr int kWideWaves = 16;
 constexpr int kFrags = 4 * 8 * 64;          // (h, ft, lane) fragments of one 128 x 128 matrix part
@@ -78,7 +66,8 @@ __device__ __forceinline__ void project_wide(f32x4 (&y)[8], const f32x4 (&xa)[8]
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int ft = 2 * fp + u;
-                y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[u], xl, y[ft], 0, 0, 0);      // small terms first
+                // small terms first, hi.lo ahead of lo.hi (not dif::mfma3's order)
+                y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[u], xl, y[ft], 0, 0, 0);
                 y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[u], xh, y[ft], 0, 0, 0);
                 y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[u], xh, y[ft], 0, 0, 0);
             }

@@ -15,23 +15,12 @@
 // float64 result).  The residual operand is rebuilt from the fragments (hi + lo = x to 2^-17).  DIFFORMER_EXACT_FP32=1 keeps
 // the layer on the library-GEMM path.
 #include <stdlib.h>
-#include "dif_common.h"
+#include "split_bf16.h"
 
 namespace {
 
 using dif::f32x4;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ void split_bf16(const f32x4& v, bf16x4& hi, bf16x4& lo) {
-    hi = __builtin_convertvector(v, bf16x4);
-    const f32x4 back = __builtin_convertvector(hi, f32x4);
-    lo = __builtin_convertvector(v - back, bf16x4);
-}
-__device__ __forceinline__ bf16x8 cat8(const bf16x4& a, const bf16x4& b) {
-    return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
+using dif::bf16x4, dif::bf16x8, dif::cat8, dif::split_bf16, dif::zero4;
 
 constexpr int kXWaves = 8;             // 128 rows per workgroup and weight chunk
 // (timing probes: a fork of this file, in the history up to commit 7ecb32a)
@@ -130,7 +119,8 @@ __global__ __launch_bounds__(64 * kXWaves, 2) void simple_layer_xwide_kernel(XAr
                     wh[u] = w[kb * 128 + u * 64 + lane];
                     wl[u] = w[KB * 128 + kb * 128 + u * 64 + lane];
                 }
-                // small terms first; the two feature tiles alternate so that no MFMA waits on the one just issued
+                // small terms first (hi.lo ahead of lo.hi: not dif::mfma3's order); the two feature tiles alternate so that no MFMA waits on
+                // the one just issued
                 y[2 * fc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[0], xl[kb], y[2 * fc], 0, 0, 0);
                 y[2 * fc + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[1], xl[kb], y[2 * fc + 1], 0, 0, 0);
                 y[2 * fc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[0], xh[kb], y[2 * fc], 0, 0, 0);

@@ -15,11 +15,12 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "dif_common.h"
+#include "split_bf16.h"
 
 namespace {
 
 using dif::f32x4;
+using dif::bf16x4, dif::bf16x8, dif::cat8, dif::mfma3, dif::split_bf16;
 using dif::Elem;
 
 // LDS weight rows hold 64 input channels (+4 floats: b128 reads of 16 rows hit all banks) for C_in <= 64, 128 (+4) for
@@ -183,17 +184,6 @@ __global__ __launch_bounds__(256) void long_linear_kernel(const T* __restrict__ 
 // 64-channel chunk is channel 32 h + 16 (s / 4) + 4 lg + s % 4 -- exactly the columns a lane already holds after its four
 // coalesced 16-byte loads of x.  W is split while it is staged: fragment (part, h, ft) of a chunk is 64 lanes x 16 bytes
 // (8 bfloat16 = the lane's eight k-slots of feature 4 l15 + ft), read back with one conflict-free ds_read_b128.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split_bf16(const f32x4& v, bf16x4& hi, bf16x4& lo) {
-    hi = __builtin_convertvector(v, bf16x4);
-    const f32x4 back = __builtin_convertvector(hi, f32x4);
-    lo = __builtin_convertvector(v - back, bf16x4);
-}
-__device__ __forceinline__ bf16x8 cat8(const bf16x4& a, const bf16x4& b) {
-    return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 
 __global__ __launch_bounds__(256) void long_linear_split_kernel(const float* __restrict__ x, int64_t ldx, int64_t n_rows, int C_in,
                                                                 const float* __restrict__ W, const float* __restrict__ bias,
@@ -274,9 +264,7 @@ __global__ __launch_bounds__(256) void long_linear_split_kernel(const float* __r
 #pragma unroll
                 for (int ft = 0; ft < 4; ++ft) {
                     const bf16x8 wh = wb[(4 * h + ft) * 64], wl = wb[(8 + 4 * h + ft) * 64];
-                    y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, wh, y[ft], 0, 0, 0);      // small terms first
-                    y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wl, y[ft], 0, 0, 0);
-                    y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wh, y[ft], 0, 0, 0);
+                    y[ft] = mfma3(xh, xl, wh, wl, y[ft]);
                 }
             }
             if (more) {
@@ -379,9 +367,7 @@ __global__ __launch_bounds__(1024) void long_linear_resident_kernel(const float*
 #pragma unroll
                 for (int ft = 0; ft < 4; ++ft) {
                     const bf16x8 wh = wb[(4 * h + ft) * 64], wl = wb[(8 + 4 * h + ft) * 64];
-                    y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, wh, y[ft], 0, 0, 0);      // small terms first
-                    y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wl, y[ft], 0, 0, 0);
-                    y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wh, y[ft], 0, 0, 0);
+                    y[ft] = mfma3(xh, xl, wh, wl, y[ft]);
                 }
             }
 #pragma unroll
@@ -402,10 +388,8 @@ __global__ __launch_bounds__(1024) void long_linear_resident_kernel(const float*
 // reads each fragment as ONE contiguous KiB (a lane picking its own elements out of W touches 16 weight rows per load
 // instruction, two cache lines each: the vector-memory tag rate then bounds the kernel at ~20 us for Cora) and there is no
 // per-tile conversion work.  Exact mode (DIFFORMER_EXACT_FP32=1): long_linear_ksplit_exact_kernel on the fp32 MFMA.
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-
 __device__ __forceinline__ f32x4 ld4_tail(const float* __restrict__ row, int c, int C_in) {
-    if (c + 3 < C_in) return *reinterpret_cast<const f32x4u*>(row + c);
+    if (c + 3 < C_in) return *reinterpret_cast<const Elem<float>::f32x4u*>(row + c);
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -469,9 +453,7 @@ __global__ __launch_bounds__(64 * kPackedWaves) void long_linear_packed_kernel(c
             const bf16x8 xh = cat8(h0, h1), xl = cat8(l0, l1);
 #pragma unroll
             for (int ft = 0; ft < 4; ++ft) {
-                y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, wf[4 * h + ft], y[ft], 0, 0, 0);      // small terms first
-                y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wf[8 + 4 * h + ft], y[ft], 0, 0, 0);
-                y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wf[4 * h + ft], y[ft], 0, 0, 0);
+                y[ft] = mfma3(xh, xl, wf[4 * h + ft], wf[8 + 4 * h + ft], y[ft]);
             }
         }
     };
@@ -781,7 +763,6 @@ __global__ __launch_bounds__(256) void skinny_linear_kernel(const T* __restrict_
 // ALIGNED dwords shifted into place (v_alignbit).  W sits in LDS as ready-made B fragments [kb][ft][lane] (feature
 // 4 l15 + ft: the epilogue's layout), zero beyond C_in.  The LAST 16-row tile reads element by element (no read past the
 // end of the tensor).
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
 template <int KB>
@@ -876,7 +857,7 @@ __global__ __launch_bounds__(256) void skinny_linear_bf16_kernel(const dif::bf16
     const int64_t last_fast = n_tiles - 2;                                  // only meaningful with fast_ok
     Raw rw[KB];
     if (fast_ok) fetch_raw(first <= last_fast ? first : last_fast, rw);
-    const bf16x8v* wfrag = reinterpret_cast<const bf16x8v*>(sm_w);
+    const bf16x8* wfrag = reinterpret_cast<const bf16x8*>(sm_w);
     for (int64_t tile = first; tile < n_tiles; tile += stride) {
         u32x4v xa[KB];
         if (fast_ok && tile <= last_fast) assemble(tile, rw, xa);
@@ -892,7 +873,7 @@ __global__ __launch_bounds__(256) void skinny_linear_bf16_kernel(const dif::bf16
         for (int ft = 0; ft < 4; ++ft) y[ft] = f32x4{bv[ft], bv[ft], bv[ft], bv[ft]};
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
-            const bf16x8v av = __builtin_bit_cast(bf16x8v, xa[kb]);
+            const bf16x8 av = __builtin_bit_cast(bf16x8, xa[kb]);
 #pragma unroll
             for (int ft = 0; ft < 4; ++ft)
                 y[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, wfrag[(kb * 4 + ft) * 64 + lane], y[ft], 0, 0, 0);

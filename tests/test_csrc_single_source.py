@@ -1,0 +1,70 @@
+"""The split-bf16 contract and the shared tile helpers are written once: csrc/split_bf16.h and csrc/dif_common.h.
+Reads the device sources as text (no compiler, no GPU) so that the per-file copies cannot grow back."""
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "difformer_amd", "csrc")
+HOMES = ("split_bf16.h", "dif_common.h")
+SHARED = ("zero4", "split_bf16", "split8", "cat8", "mfma3", "dinv_of", "tile_product", "ld4", "ld4_raw", "mask4", "sigmoid_hw")
+
+# `typedef __bf16 name __attribute__((ext_vector_type(n)))`, `using name = __bf16 __attribute__((...))`, and the same through
+# the other spellings of the element type
+BF16_VECTOR = re.compile(r"\b(?:typedef\s+(?:__bf16|__hip_bfloat16|hip_bfloat16)\b[^;]*vector_type|using\s+\w+\s*=\s*(?:__bf16|__hip_bfloat16|hip_bfloat16)\b[^;]*vector_type)")
+
+
+def sources():
+    out = {}
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".hip", ".h")):
+            text = open(os.path.join(CSRC, name)).read()
+            text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+            out[name] = re.sub(r"//[^\n]*", "", text)
+    return out
+
+
+def definitions(text, name):
+    """Free functions called `name` that have a body.  A definition is `<qualifiers and return type> name(<parameters>) {`
+    with a device / inline qualifier in front; the static member functions of dif::Elem<T> (ld4 among them) are not meant."""
+    found = []
+    for m in re.finditer(r"^[^\n;=(]*\b(?:__device__|__host__|__forceinline__|inline)\b[^\n;=(]*[\s&*]%s\s*\(" % re.escape(name), text, flags=re.M):
+        if re.search(r"\bstatic\b", m.group(0)):
+            continue
+        depth, i = 1, m.end()
+        while depth:                            # the matching parenthesis of the parameter list
+            depth += {"(": 1, ")": -1}.get(text[i], 0)
+            i += 1
+        if re.match(r"\s*(?:const\s*)?\{", text[i:]):
+            found.append(m.group(0).strip())
+    return found
+
+
+def test_the_sources_are_where_the_test_looks():
+    src = sources()
+    assert set(HOMES) <= set(src) and len([n for n in src if n.endswith(".hip")]) >= 25
+
+
+def test_bf16_vector_types_are_declared_in_split_bf16_h_only():
+    src = sources()
+    assert len(BF16_VECTOR.findall(src["split_bf16.h"])) == 2            # bf16x4, bf16x8
+    offenders = {n: BF16_VECTOR.findall(t) for n, t in src.items() if n != "split_bf16.h" and BF16_VECTOR.search(t)}
+    assert not offenders, offenders
+
+
+def test_no_kernel_file_defines_a_shared_helper():
+    offenders = {(n, name): d for n, t in sources().items() if n not in HOMES for name in SHARED for d in [definitions(t, name)] if d}
+    assert not offenders, offenders
+
+
+def test_every_shared_helper_is_defined_exactly_once():
+    src = sources()
+    counts = {name: sum(len(definitions(src[h], name)) for h in HOMES) for name in SHARED}
+    assert counts == {name: 1 for name in SHARED}, counts
+
+
+def test_the_definition_finder_sees_a_copy():
+    copy = "namespace {\ntemplate <bool VEC>\n__device__ __forceinline__ f32x4 ld4(const float* __restrict__ base, int64_t ld,\n   int width) {\n    return f32x4{};\n}\n}"
+    assert len(definitions(copy, "ld4")) == 1 and not definitions(copy, "ld4_raw")
+    assert not definitions("    z = ld4<VEC>(base, ld, rc, rok, col0, c, width);\n    if (x) split8(a, b, hi, lo);", "ld4")
+    assert BF16_VECTOR.search("typedef __bf16 my8 __attribute__((ext_vector_type(8)));")
+    assert BF16_VECTOR.search("using my8 = __bf16 __attribute__((ext_vector_type(8)));")
