@@ -8,11 +8,11 @@ from __future__ import annotations
 
 import ctypes
 import os
-import weakref
 
 import torch
 
 from . import _lib
+from .tensor_cache import MISS, TensorCache
 
 
 def _ptr(t):
@@ -190,6 +190,7 @@ class HipBackend:
         self.kernel_events = None
         self.kernel_events_only = None
         self._ones = {}                             # device -> float32 [1] = 1.0 (device-side beta of dif_rowgemm_f32)
+        self._packed = TensorCache(64)              # weight tensor, geometry -> its packed copy (_cached_pack)
         from . import ops
         self.lib.dif_set_exact_fp32(1 if ops.EXACT_FP32 else 0)      # a set_exact_fp32 made before the library was loaded
 
@@ -954,20 +955,15 @@ class HipBackend:
         return out
 
     def _cached_pack(self, tensor, geometry, pack):
-        """pack() -> packed copy of a weight `tensor`, cached per tensor and `geometry` (a tuple): identity through a weak
-        reference + data_ptr + version, like the CSR cache (a new tensor at a recycled address must not find the old
-        packing).  Rebuilt after optimiser steps / load_state_dict (they bump the version); `.data` writes need
-        model.invalidate_caches(); a tensor without a version (< 0) is packed every time."""
-        from . import ops
-        ver = ops.tensor_version(tensor)
-        key = (id(tensor), tensor.data_ptr(), ver) + geometry
-        cache = self.__dict__.setdefault("_packed", {})
-        hit = cache.get(key)
-        if hit is not None and ver >= 0 and hit[0]() is tensor:
-            return self._pin(hit[1])
-        packed = pack()
-        if ver >= 0:
-            self._packed_insert(cache, key, tensor, packed)
+        """pack() -> packed copy of a weight `tensor`, cached per tensor and `geometry` (a tuple) in a TensorCache (a new
+        tensor at a recycled address must not find the old packing).  Rebuilt after optimiser steps / load_state_dict (they
+        bump the version, and the insert drops the older version's entry: an optimiser step per epoch adds none); `.data`
+        writes need model.invalidate_caches(); a tensor without a version is packed every time.  The cache is never emptied
+        behind a captured hipGraph's back: a capture bakes raw pointers to these buffers in and pins the ones it used
+        itself (`capture_pins`)."""
+        packed = self._packed.lookup((tensor,), geometry)
+        if packed is MISS:
+            packed = self._packed.insert((tensor,), geometry, pack())
         return self._pin(packed)
 
     def _packed_weight(self, weight, C, Co, dev):
@@ -977,17 +973,6 @@ class HipBackend:
             self._call("dif_linear_pack_f32", "dif_linear_pack_f32", dev, _ptr(weight), C, Co, _ptr(packed))
             return packed
         return self._cached_pack(weight, (C, Co, str(dev)), pack)
-
-    @staticmethod
-    def _packed_insert(cache, key, tensor, packed):
-        """Insert into a packed-weight cache.  Evicted: entries of freed tensors and OLDER VERSIONS of this tensor (an optimiser
-        step per epoch would otherwise add an entry per epoch); beyond 64 live entries the oldest.  Never everything at once:
-        a captured hipGraph bakes raw pointers to these buffers in (it pins the ones it used itself, `capture_pins`)."""
-        for k in [k for k, v in cache.items() if v[0]() is None or (v[0]() is tensor and k[:2] == key[:2] and k[3:] == key[3:])]:
-            del cache[k]
-        while len(cache) >= 64:
-            del cache[next(iter(cache))]
-        cache[key] = (weakref.ref(tensor), packed)
 
     def _pin(self, packed):
         """While a forward is being captured, the capture keeps every packed buffer it was handed alive (DIFFormer.

@@ -14,7 +14,6 @@ result back on the host (staging.py); without a GPU such a call raises.
 from __future__ import annotations
 
 import os
-import weakref
 
 import torch
 import torch.nn as nn
@@ -24,6 +23,7 @@ from . import ops
 from . import autograd_ops as ag
 from . import staging
 from . import tiny
+from .tensor_cache import same_tensors, tensor_key, weak_refs
 
 __all__ = ["full_attention_conv", "gcn_conv", "DIFFormerConv", "DIFFormer"]
 
@@ -475,11 +475,11 @@ class DIFFormer(nn.Module):
                 return None
             key.append((id(c), c.kernel, c.use_graph, c.use_weight, c.use_source, c.graph_weight, c.num_heads, c.out_channels))
             lin.extend(c._modules.values())              # Wk, Wq (, Wv)
-        for t in (edge_index, edge_weight):
-            key.append(None if t is None else (id(t), t.data_ptr(), t.shape, ops.tensor_version(t)))
+        key.append(tensor_key(edge_index))
+        key.append(tensor_key(edge_weight))
         for m in lin:
             for p in m._parameters.values():
-                key.append((id(p), p.data_ptr(), ops.tensor_version(p)) if p is not None else None)
+                key.append(tensor_key(p))
         return tuple(key)
 
     def _forward_graphed(self, x, edge_index, edge_weight):
@@ -501,12 +501,10 @@ class DIFFormer(nn.Module):
         if key is None:
             return None
         st = self._ag_state
-        # (id, data_ptr, shape, version) of a freed graph tensor can all come back with a NEW tensor: weak references tell
-        # the tensors the capture was made for from look-alikes, as in the CSR cache
-        alive = st is not None and all((r is None) == (t is None) and (r is None or r() is t)
-                                       for r, t in zip(st[5], (edge_index, edge_weight)))
-        if st is None or st[0] != key or not alive:
-            refs = tuple(None if t is None else weakref.ref(t) for t in (edge_index, edge_weight))
+        # the key of a freed graph tensor can come back with a NEW tensor: weak references tell the tensors the capture was
+        # made for from look-alikes (tensor_cache)
+        if st is None or st[0] != key or not same_tensors(st[5], (edge_index, edge_weight)):
+            refs = weak_refs((edge_index, edge_weight))
             self._ag_state = [key, 1, None, None, None, refs]        # key, calls seen, graph, static output, CSR refs, tensors
             return None
         if st[2] is None:
@@ -530,7 +528,7 @@ class DIFFormer(nn.Module):
                 be.capture_pins = None
             # the captured kernels hold raw pointers into the cached CSR / formats: they live as long as the capture
             st[2], st[3] = graph, out
-            st[4] = ([v[2] for v in ops.csr_cache.entries.values()] if edge_index is not None else []) + pins
+            st[4] = (ops.csr_cache.values() if edge_index is not None else []) + pins
         st[2].replay()
         return st[3].clone()
 
@@ -551,7 +549,7 @@ class DIFFormer(nn.Module):
         mix = None
         conv0 = self.convs[0] if len(self.convs) else None
         if (conv0 is not None and conv0.use_graph and edge_index is not None and edge_weight is None and conv0.row_shard is None
-                and x.dtype == torch.float32 and x.is_cuda and hasattr(ops, "mix_cache")):
+                and x.dtype == torch.float32 and x.is_cuda):
             # columns the aggregation runs on: the value tensor [n, H, D] (or the layer input itself without Wv)
             width = conv0.out_channels * (conv0.num_heads if conv0.use_weight else 1)
             mix = ops.mix_cache.get(edge_index, x.shape[0], width)

@@ -48,7 +48,7 @@ class GraphedForward:
                     model(self.x, edge_index, edge_weight)
             torch.cuda.current_stream(dev).wait_stream(side)
             # the captured kernels hold raw pointers into the CSR: keep it alive with this object
-            self._csr = [v[2] for v in ops.csr_cache.entries.values()] if edge_index is not None else []
+            self._csr = ops.csr_cache.values() if edge_index is not None else []
             be = ops.get_backend()
             self._pins = []                  # ... and into packed weight buffers (backend `capture_pins`)
             be.capture_pins = self._pins
@@ -61,7 +61,7 @@ class GraphedForward:
             # the other derived tensors the captured kernels read: concatenated projections, weight-only factors, float32
             # copies of bfloat16 parameters -- a later eager call with changed parameters replaces them in their caches
             self._pins.append([(c._fused_wb, c._wide, c._narrow) for c in getattr(model, "convs", [])])
-            self._pins.append([v[1] for v in ops._F32_PARAMS.values()])
+            self._pins.append(ops._F32_PARAMS.values())
 
     def __call__(self, x=None):
         if x is not None:
@@ -90,7 +90,7 @@ def graphed_training(model, x, edge_index=None, edge_weight=None, warmup=3):
         model(*args)                      # loads the library, builds and caches the CSR outside the capture
     graphed = torch.cuda.make_graphed_callables(model, args, num_warmup_iters=max(3, int(warmup)))
     # the captured kernels hold raw pointers into the CSR (and its adjoint, built by the warm-up backward passes)
-    graphed._difformer_csr = [v[2] for v in ops.csr_cache.entries.values()] if edge_index is not None else []
+    graphed._difformer_csr = ops.csr_cache.values() if edge_index is not None else []
     graphed.train(was_training)
     return graphed
 
@@ -131,7 +131,7 @@ class GraphedTrainStep:
                 optimizer.zero_grad(set_to_none=True)
                 one_step()
         torch.cuda.current_stream(dev).wait_stream(side)
-        self._csr = [v[2] for v in ops.csr_cache.entries.values()] if edge_index is not None else []
+        self._csr = ops.csr_cache.values() if edge_index is not None else []
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)             # gradients are re-created inside the capture's memory pool
         with torch.cuda.graph(self.graph):

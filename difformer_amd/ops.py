@@ -10,7 +10,6 @@ adds the single exchange step the operator needs (dist.py).
 from __future__ import annotations
 
 import weakref
-from collections import OrderedDict
 from typing import Optional
 
 import math
@@ -19,31 +18,9 @@ import os
 import torch
 
 from .dist import RowShard
+from .tensor_cache import MISS, TensorCache, param_key, tensor_version      # (both functions are part of this module's surface)
 
 _BACKEND = None
-
-
-def tensor_version(t):
-    """`t._version`, or -1 for tensors that do not track one (created under torch.inference_mode())."""
-    try:
-        return t._version
-    except RuntimeError:
-        return -1
-
-
-def param_key(params):
-    """Identity + version key of a list of parameters for the inference-time caches (concatenated projections,
-    weight-only factors of the closed form, float32 copies), or None when a version cannot be read (inference tensors):
-    the caller then rebuilds instead of caching.  NOTE: writes through `.data` (`p.data.copy_()`, EMA / weight averaging
-    done on `.data`) do NOT bump the version counter -- call `model.invalidate_caches()` after such an update
-    (`load_state_dict` and `.to()` / `.half()` / ... do it themselves)."""
-    key = []
-    for t in params:
-        v = tensor_version(t)
-        if v < 0:
-            return None
-        key.append((t.data_ptr(), v, t.dtype, t.device))
-    return tuple(key)
 
 
 def get_backend():
@@ -374,10 +351,7 @@ class GraphCSR:
         A_hat (x Wv^T + 1 bv^T) = (A_hat x) Wv^T + (A_hat 1) bv^T.  One small product per graph, cached."""
         if self._row_sums is None:
             ones = torch.ones((self.num_nodes, 4), dtype=torch.float32, device=self.rowptr.device)
-            be = get_backend()
-            out = be.spmm(self.rowptr, self.blkptr, self.n_blocks, self.src, self.val, self.num_nodes, self.nnz, ones, 0,
-                          self.num_nodes, None, 1.0, 1.0, None, self.row_order(0, self.num_nodes))
-            self._row_sums = out[:, 0].contiguous()
+            self._row_sums = _aggregate_rows(get_backend(), self, None, ones, 0, self.num_nodes)[:, 0].contiguous()
         return self._row_sums
 
     def max_degree(self):
@@ -427,23 +401,15 @@ class GraphCSR:
         return self._adjoint
 
 
-class _CSRCache:
+class _CSRCache(TensorCache):
     """The reference rebuilds degree / values / SparseTensor in every layer of every forward
     (difformer.py:66-75).  We key the built CSR on the identity *and* version of the tensors the
-    caller passes, so `forward(x, edge_index)` keeps its signature and in-place edits or new
-    tensors still trigger a rebuild."""
+    caller passes (TensorCache: edge_index and the edge_weight GIVEN, with num_nodes and the blocking), so
+    `forward(x, edge_index)` keeps its signature and in-place edits or new tensors still trigger a rebuild."""
 
     def __init__(self, capacity=8):
-        self.capacity = capacity
-        self.entries = OrderedDict()
-
-    @staticmethod
-    def _key(edge_index, edge_weight, num_nodes, n_blocks, block_rows=0):
-        k = (id(edge_index), edge_index.data_ptr(), tuple(edge_index.shape), tensor_version(edge_index), int(num_nodes),
-             int(n_blocks), int(block_rows), str(edge_index.device))
-        if edge_weight is not None:
-            k += (id(edge_weight), edge_weight.data_ptr(), tensor_version(edge_weight))
-        return k
+        super().__init__(capacity, unversioned=True)
+        self._uniform = TensorCache(64)           # edge_weight tensor -> the constant all its entries equal, or None
 
     def get(self, edge_index, edge_weight, num_nodes, row_bytes=256, shard=None, elem_size=4, build_format=True):
         """`row_bytes` = bytes of one feature row the SpMM will gather (H*D*elem_size); picks the blocking -- the
@@ -456,7 +422,9 @@ class _CSRCache:
             # row-sharded it would need the gathered rows of both operands on every rank
             raise NotImplementedError("difformer_amd: gradients with respect to edge_weight are not implemented for "
                                       "row-sharded runs; detach() it or keep it a constant of the graph")
-        self._purge()
+        # entries of freed edge tensors go NOW: a mini-batch loop (main-batch.py:126-131) makes a new edge_index per batch,
+        # and a dead entry would otherwise pin its CSR (and sliced format) in HBM until the next build
+        self.purge()
         # every weight equal (one reduction, read with the host read a build has anyway): value_e = w d_in d_out
         # (difformer.py:73) = w x the unweighted value, so the graph takes every UNWEIGHTED kernel (feature-sliced product,
         # in-layer aggregation) and w rides in the callers' gcn_scale.  Keyed like a weighted graph, built like an unweighted one.
@@ -466,27 +434,17 @@ class _CSRCache:
             if u is not None:
                 edge_weight, scale = None, u
         n_blocks, block_rows = self.blocking(edge_index, edge_weight, num_nodes, row_bytes, shard, elem_size)
-        key = self._key(edge_index, given_weight, num_nodes, n_blocks, block_rows)
-        hit = self.entries.get(key)
-        csr = None
-        if hit is not None:
-            ei_ref, ew_ref, csr = hit
-            if ei_ref() is edge_index and (given_weight is None or ew_ref() is given_weight):
-                if edge_weight is not None and not csr.weighted:
-                    # built through the uniform-weight shortcut (an eval pass before the first step of learnable weights
-                    # initialised to a constant): this call wants the weighted CSR, whose values autograd differentiates
-                    del self.entries[key]
-                    csr = None
-                else:
-                    self.entries.move_to_end(key)
-                    if csr._format_checked or not build_format:
-                        return csr
-            else:
-                del self.entries[key]
-                csr = None
-        if csr is None:
+        tensors, extras = (edge_index, given_weight), (int(num_nodes), int(n_blocks), int(block_rows))
+        csr = self.lookup(tensors, extras)
+        if csr is not MISS and edge_weight is not None and not csr.weighted:
+            # built through the uniform-weight shortcut (an eval pass before the first step of learnable weights
+            # initialised to a constant): this call wants the weighted CSR, whose values autograd differentiates
+            csr = MISS
+        if csr is MISS:
             csr = GraphCSR.build(edge_index, edge_weight, num_nodes, n_blocks, block_rows=block_rows)
             csr.weight_scale = scale
+        elif csr._format_checked or not build_format:
+            return csr
         F = row_bytes // elem_size
         if build_format:
             # (also the first `build_format` request for a CSR that a pointers-only probe left here: _MixCache.get)
@@ -510,11 +468,7 @@ class _CSRCache:
                     csr = GraphCSR.build(edge_index, edge_weight, num_nodes, nb2, block_rows=br2)
                     csr._format_checked = True
                     csr.weight_scale = scale
-        self.entries[key] = (weakref.ref(edge_index), weakref.ref(given_weight) if given_weight is not None else None,
-                             csr)
-        while len(self.entries) > max(self.capacity, getattr(self, "_floor", 0)):
-            self.entries.popitem(last=False)
-        return csr
+        return self.insert(tensors, extras, csr)
 
     UNIFORM_ALWAYS = False       # tests: run the check on graphs of any size
     UNIFORM_MIN_EDGES = 4096     # below this the CSR build is a handful of launches and the check would double its host cost
@@ -532,13 +486,9 @@ class _CSRCache:
             return None
         if edge_weight.requires_grad and torch.is_grad_enabled():
             return None
-        memo = self.__dict__.setdefault("_uniform", OrderedDict())
-        key = (id(edge_weight), edge_weight.data_ptr(), tensor_version(edge_weight), n_edges)
-        hit = memo.get(key)
-        if hit is not None and hit[0]() is edge_weight and key[2] >= 0:
-            return hit[1]
-        for k in [k for k, v in memo.items() if v[0]() is None]:
-            del memo[k]
+        u = self._uniform.lookup((edge_weight,), (n_edges,))
+        if u is not MISS:
+            return u
         w = edge_weight.detach()
         lo, hi = torch.stack([w.min(), w.max()]).tolist()            # NaN anywhere -> both NaN -> lo == hi is False
         if lo == hi:
@@ -547,10 +497,7 @@ class _CSRCache:
             u = 0.0
         else:
             u = None
-        memo[key] = (weakref.ref(edge_weight), u)
-        while len(memo) > 64:
-            memo.popitem(last=False)
-        return u
+        return self._uniform.insert((edge_weight,), (n_edges,), u)
 
     @staticmethod
     def blocking(edge_index, edge_weight, num_nodes, row_bytes=256, shard=None, elem_size=4):
@@ -565,32 +512,11 @@ class _CSRCache:
     def put(self, edge_index, edge_weight, num_nodes, csr):
         """Register a CSR built elsewhere (graph_utils.subgraph_batches: all batches of an epoch from one sort) under the
         key `get` would use for these tensors, so that `model(x_i, edge_index_i)` finds it without building anything."""
-        key = self._key(edge_index, edge_weight, num_nodes, csr.n_blocks, 0)
-        self.entries[key] = (weakref.ref(edge_index), weakref.ref(edge_weight) if edge_weight is not None else None, csr)
-        self.entries.move_to_end(key)
-        while len(self.entries) > max(self.capacity, getattr(self, "_floor", 0)):
-            self.entries.popitem(last=False)
+        self.insert((edge_index, edge_weight), (int(num_nodes), int(csr.n_blocks), 0), csr)
 
-    def drop(self, edge_index):
-        """Forget every CSR built from this edge_index tensor (frees its HBM once no autograd node holds it)."""
-        for k in [k for k, (ei_ref, _, _) in self.entries.items() if ei_ref() is edge_index]:
-            del self.entries[k]
-
-    def reserve(self, n):
-        """Keep room for at least n entries (an epoch's worth of registered batches must not evict one another)."""
-        self._floor = max(int(n), 0)
-
-    def _purge(self):
-        """Drop entries whose edge tensors have been freed: a mini-batch loop (main-batch.py:126-131) makes a new
-        edge_index per batch, and a dead entry would otherwise pin its CSR (and sliced format) in HBM until eight
-        newer graphs push it out."""
-        dead = [k for k, (ei_ref, ew_ref, _) in self.entries.items()
-                if ei_ref() is None or (ew_ref is not None and ew_ref() is None)]
-        for k in dead:
-            del self.entries[k]
-
-    def clear(self):
-        self.entries.clear()
+    # From TensorCache: drop(edge_index) forgets every CSR built from that tensor (its HBM is freed once no autograd node
+    # holds it), reserve(n) keeps an epoch's worth of registered batches from evicting one another, values() are the CSRs
+    # held (what a hipGraph capture keeps alive).
 
 
 _SLICED_FALLBACK_WARNED = False
@@ -622,20 +548,13 @@ class MixedGraph:
         self.edge_index = self.inv[edge_index]              # same edges, same order, nodes renamed
 
 
-class _MixCache:
-    """MixedGraph (or the decision not to mix) per edge_index tensor, keyed like the CSR cache."""
-
-    def __init__(self, capacity=8):
-        self.capacity, self.entries = capacity, OrderedDict()
+class _MixCache(TensorCache):
+    """MixedGraph (or None: the decision not to mix) per edge_index tensor, num_nodes and width."""
 
     def get(self, edge_index, num_nodes, F):
-        key = (id(edge_index), edge_index.data_ptr(), tuple(edge_index.shape), tensor_version(edge_index), int(num_nodes), int(F))
-        hit = self.entries.get(key)
-        if hit is not None and hit[0]() is edge_index:
-            self.entries.move_to_end(key)
-            return hit[1]
-        for k in [k for k, v in self.entries.items() if v[0]() is None]:
-            del self.entries[k]
+        mix = self.lookup((edge_index,), (int(num_nodes), int(F)))
+        if mix is not MISS:
+            return mix
         mix = None
         if sliced_tiling(num_nodes, F, edge_index.shape[1], None, None, 4) is not None:
             csr = csr_cache.get(edge_index, None, num_nodes, F * 4, build_format=False)     # probe: pointers only
@@ -646,16 +565,30 @@ class _MixCache:
                 if share > MIX_THRESHOLD:
                     mix = MixedGraph(edge_index, num_nodes)
                     csr_cache.drop(edge_index)      # the forward runs on the relabelled graph: the probe CSR is dead weight
-        self.entries[key] = (weakref.ref(edge_index), mix)
-        while len(self.entries) > self.capacity:
-            self.entries.popitem(last=False)
-        return mix
-
-    def clear(self):
-        self.entries.clear()
+        return self.insert((edge_index,), (int(num_nodes), int(F)), mix)
 
 
-mix_cache = _MixCache()
+mix_cache = _MixCache(8, unversioned=True)
+
+
+def _aggregate_rows(be, csr, sl, x_src, row_begin, n_rows, attn=None, attn_scale=1.0, gcn_scale=1.0, tail=None, ys=None):
+    """gcn_scale * A_hat[row_begin : row_begin + n_rows] x_src (+ attn_scale * attn) (-> tail): the one call sequence of
+    the aggregation, x_src [num_nodes, F] -> [n_rows, F].
+    sl = csr.sliced(row_begin, n_rows, F) of a dense unweighted graph: the sources pre-scaled (`ys`: that copy, when a layer
+    kernel has written it already) and staged slice by slice in LDS (csrc/gcn_sliced.hip); the LayerNorm of the tail needs
+    whole rows, which the slice workgroups do not have: it runs as its own pass.
+    sl = None: the gather kernels, the tail in their epilogue."""
+    if sl is None:
+        return be.spmm(csr.rowptr, csr.blkptr, csr.n_blocks, csr.src, csr.val, csr.num_nodes, csr.nnz, x_src, row_begin, n_rows,
+                       attn, attn_scale, gcn_scale, tail, csr.row_order(row_begin, n_rows))
+    F = x_src.shape[1]
+    if ys is None:
+        ys = be.sliced_prescale(x_src, csr.rowptr, csr.num_nodes, sl.plan, csr.dinv)
+    out = be.sliced_spmm(sl, ys, csr.rowptr, csr.num_nodes, row_begin, n_rows, F, attn, attn_scale, gcn_scale, csr.dinv)
+    if tail is not None:                       # (one head: F = D)
+        out = be.layer_tail(out.reshape(n_rows, 1, F), tail.get("x0"), tail.get("prev"), tail.get("alpha", 0.5),
+                            tail.get("ln_weight"), tail.get("ln_bias"), tail.get("eps", 1e-5), tail.get("relu", False))
+    return out
 
 
 def gcn_aggregate(csr: GraphCSR, x, attn=None, attn_scale=1.0, gcn_scale=1.0, shard: Optional[RowShard] = None,
@@ -667,25 +600,11 @@ def gcn_aggregate(csr: GraphCSR, x, attn=None, attn_scale=1.0, gcn_scale=1.0, sh
     layer tail of :139-140 / :200-203 into the SpMM epilogue; the result is then [n, 1, D]."""
     n, H, D = x.shape
     be = get_backend()
-    args = (csr.rowptr, csr.blkptr, csr.n_blocks, csr.src, csr.val, csr.num_nodes, csr.nnz)
     flat = lambda a: None if a is None else (a.materialize() if isinstance(a, LazyAttention) else a).reshape(n, H * D)
     if shard is None or shard.world <= 1:
-        a2 = flat(attn)
-        x2 = x.reshape(n, H * D)
         sl = csr.sliced(0, n, H * D) if (x.dtype == torch.float32 and n == csr.num_nodes) else None
-        if sl is not None:
-            # dense unweighted graph: sources pre-scaled and staged slice by slice in LDS (csrc/gcn_sliced.hip); the
-            # LayerNorm of the tail needs whole rows, which the slice workgroups do not have: it runs as its own pass
-            ys = be.sliced_prescale(x2, csr.rowptr, csr.num_nodes, sl.plan, csr.dinv)
-            out = be.sliced_spmm(sl, ys, csr.rowptr, csr.num_nodes, 0, n, H * D, a2, attn_scale, gcn_scale, csr.dinv)
-            if tail is not None:
-                out = be.layer_tail(out.reshape(n, H, D), tail.get("x0"), tail.get("prev"), tail.get("alpha", 0.5),
-                                    tail.get("ln_weight"), tail.get("ln_bias"), tail.get("eps", 1e-5),
-                                    tail.get("relu", False))
-                return out.reshape(n, 1, D)
-            return out.reshape(n, H, D)
-        out = be.spmm(*args, x2, 0, n, a2, attn_scale, gcn_scale, tail, csr.row_order(0, n))
-        return out.reshape(n, H, D)
+        out = _aggregate_rows(be, csr, sl, x.reshape(n, H * D), 0, n, flat(attn), attn_scale, gcn_scale, tail)
+        return out.reshape(n, -1, D)           # [n, H, D]; [n, 1, D] after a tail
     # row-sharded: the one exchange step of this operator is the all-gather of the value rows (N*H*D elements)
     if isinstance(x, GatheredRows):            # already started by project_simple_attention
         local, handle = x.local.reshape(n, H * D), x.handle
@@ -694,28 +613,19 @@ def gcn_aggregate(csr: GraphCSR, x, attn=None, attn_scale=1.0, gcn_scale=1.0, sh
         handle = shard.all_gather_rows_async(local)
     row_begin, n_rows = shard.row_begin, shard.n_local
     F = H * D
+    # dense unweighted graph: the shard's feature-sliced product (source tiles split over the workgroups of a panel) over
+    # the gathered rows, as in the single-GPU branch above
     sl = csr.sliced(row_begin, n_rows, F) if local.dtype == torch.float32 else None
-    if sl is not None:
-        # dense unweighted graph: the shard's feature-sliced product (source tiles split over the workgroups of a panel)
-        # over the gathered rows, as in the single-GPU branch above
-        a2 = flat(attn)                        # waits for the record all-reduce, runs `apply` under the all-gather
-        x2 = handle.wait()
-        ys = be.sliced_prescale(x2, csr.rowptr, csr.num_nodes, sl.plan, csr.dinv)
-        out = be.sliced_spmm(sl, ys, csr.rowptr, csr.num_nodes, row_begin, n_rows, F, a2, attn_scale, gcn_scale, csr.dinv)
-        if tail is not None:
-            out = be.layer_tail(out.reshape(n_rows, H, D), tail.get("x0"), tail.get("prev"), tail.get("alpha", 0.5),
-                                tail.get("ln_weight"), tail.get("ln_bias"), tail.get("eps", 1e-5), tail.get("relu", False))
-            return out.reshape(n_rows, 1, D)
-        return out.reshape(n_rows, H, D)
-    order = csr.row_order(row_begin, n_rows)
+    order = csr.row_order(row_begin, n_rows) if sl is None else None      # (built here, under the collective, on first use)
     rows = csr.block_rows
-    split = (csr.n_blocks > 1 and csr.nnz > 0 and F % 4 == 0 and F <= 256 and row_begin % rows == 0 and
+    split = (sl is None and csr.n_blocks > 1 and csr.nnz > 0 and F % 4 == 0 and F <= 256 and row_begin % rows == 0 and
              (row_begin + n_rows == csr.num_nodes or (row_begin + n_rows) % rows == 0))
     if split:
         # blocks [own_lo, own_hi) hold exactly this rank's own value rows: sweep them now, under the collective, and
         # park the accumulators; the rest of the sweep and the epilogue follow once the other ranks' rows have landed
         own_lo, own_hi = row_begin // rows, -(-(row_begin + n_rows) // rows)
         local = local if local.is_contiguous() else local.contiguous()
+        args = (csr.rowptr, csr.blkptr, csr.n_blocks, csr.src, csr.val, csr.num_nodes, csr.nnz)
         scratch = be.spmm(*args, local, row_begin, n_rows, None, attn_scale, gcn_scale, None, order,
                           (0, own_lo, own_hi, None, row_begin))
         a2 = flat(attn)                        # waits for the record all-reduce, runs `apply` -- after part 0 is queued
@@ -723,10 +633,9 @@ def gcn_aggregate(csr: GraphCSR, x, attn=None, attn_scale=1.0, gcn_scale=1.0, sh
         out = be.spmm(*args, x2, row_begin, n_rows, a2, attn_scale, gcn_scale, tail, order,
                       (1, own_lo, own_hi, scratch, 0))
     else:
-        a2 = flat(attn)
-        x2 = handle.wait()
-        out = be.spmm(*args, x2, row_begin, n_rows, a2, attn_scale, gcn_scale, tail, order)
-    return out.reshape(n_rows, H, D)
+        a2 = flat(attn)                        # waits for the record all-reduce, runs `apply` under the all-gather
+        out = _aggregate_rows(be, csr, sl, handle.wait(), row_begin, n_rows, a2, attn_scale, gcn_scale, tail)
+    return out.reshape(n_rows, -1, D)          # [n_rows, H, D]; [n_rows, 1, D] after a tail
 
 
 class NarrowFactors:
@@ -775,26 +684,17 @@ SIDE_CHAIN = os.environ.get("DIFFORMER_SIDE_CHAIN", "1") != "0"
 # extra product is a split-bfloat16 one) but runs as its own fp32-MFMA launch.  Results move by ~4e-6 of the logits' scale.
 EXACT_FP32 = os.environ.get("DIFFORMER_EXACT_FP32", "0") == "1"
 
-_F32_PARAMS = OrderedDict()
+_F32_PARAMS = TensorCache(256)
 
 
 def f32_param(t):
-    """Exact float32 copy of a bfloat16 parameter, cached until the parameter changes (identity + version keyed, like
-    the CSR cache); float32 tensors pass through.  The closed-form kernels take their coefficients in float32."""
+    """Exact float32 copy of a bfloat16 parameter, cached until the parameter changes (TensorCache); float32 tensors
+    pass through.  The closed-form kernels take their coefficients in float32."""
     if t is None or t.dtype == torch.float32:
         return t
-    ver = tensor_version(t)
-    if ver < 0:
-        return t.detach().to(torch.float32).contiguous()       # version unreadable (inference tensor): never cached
-    key = (id(t), t.data_ptr(), ver, tuple(t.shape), str(t.device))
-    hit = _F32_PARAMS.get(key)
-    if hit is not None and hit[0]() is t:
-        _F32_PARAMS.move_to_end(key)
-        return hit[1]
-    c = t.detach().to(torch.float32).contiguous()
-    _F32_PARAMS[key] = (weakref.ref(t), c)
-    while len(_F32_PARAMS) > 256:
-        _F32_PARAMS.popitem(last=False)
+    c = _F32_PARAMS.lookup((t,))
+    if c is MISS:
+        c = _F32_PARAMS.insert((t,), (), t.detach().to(torch.float32).contiguous())
     return c
 
 
@@ -802,8 +702,9 @@ def invalidate_param_caches():
     """Forget the cached float32 copies of bfloat16 parameters and the packed weights of the long-row Linear (see
     param_key for when this is needed)."""
     _F32_PARAMS.clear()
-    if _BACKEND is not None and hasattr(_BACKEND, "_packed"):
-        _BACKEND._packed.clear()
+    packed = getattr(_BACKEND, "_packed", None)      # (HipBackend's; a host-side test backend packs nothing and has none)
+    if packed is not None:
+        packed.clear()
 
 
 def slice_sharded(shard, C, dtype=torch.float32):
@@ -826,13 +727,7 @@ def _closed_form_slice_sharded(be, x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, g
     record, _ = be.gram(x, None, None)                                      # local rows; runs while the exchange lands
     shard.all_reduce_sum(record)
     coef = be.simple_coeffs(record, N, C, D, Wq, bq, Wk, bk, Wv, bv, attn_scale)
-    sl = csr.sliced(0, N, w) if hasattr(csr, "sliced") else None
-    if sl is not None:
-        ys = be.sliced_prescale(xs, csr.rowptr, N, sl.plan)
-        axs = be.sliced_spmm(sl, ys, csr.rowptr, N, 0, N, w, None, 1.0, gcn_scale)
-    else:
-        axs = be.spmm(csr.rowptr, csr.blkptr, csr.n_blocks, csr.src, csr.val, N, csr.nnz, xs, 0, N, None, 1.0, gcn_scale,
-                      None, csr.row_order(0, N))
+    axs = _aggregate_rows(be, csr, csr.sliced(0, N, w), xs, 0, N, gcn_scale=gcn_scale)
     ax = shard.all_to_all_rows(axs)                                         # [n, C]: every column block of my rows
     rs = None
     if Wv is not None:
@@ -910,16 +805,10 @@ def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_sca
         gather = (csr.rowptr, csr.src, csr.val)
     elif csr is not None:
         x_src = handle.wait() if sharded else x
-        if sl is not None:
-            if ys is None:
-                ys = be.sliced_prescale(x_src, csr.rowptr, csr.num_nodes, sl.plan)
-            ax = be.sliced_spmm(sl, ys, csr.rowptr, csr.num_nodes, row_begin, n, C, None, 1.0, gcn_scale)
-            if join is not None:
-                with torch.cuda.stream(join[1]):
-                    coef = be.coeffs_bg(None if record is not None else x, record, n_global, factors, C, D, attn_scale)
-        else:
-            ax = be.spmm(csr.rowptr, csr.blkptr, csr.n_blocks, csr.src, csr.val, csr.num_nodes, csr.nnz, x_src, row_begin, n,
-                         None, 1.0, gcn_scale, None, csr.row_order(row_begin, n))
+        ax = _aggregate_rows(be, csr, sl, x_src, row_begin, n, gcn_scale=gcn_scale, ys=ys)
+        if join is not None:                       # (only with the sliced product: `background`)
+            with torch.cuda.stream(join[1]):
+                coef = be.coeffs_bg(None if record is not None else x, record, n_global, factors, C, D, attn_scale)
         if Wv is not None:
             rs = csr.row_sums()
             if sharded:
@@ -1133,37 +1022,22 @@ class BatchLayout:
         self.pos_count = (self.n_graphs - le[:biggest]).to(torch.int32).contiguous()
 
 
-class _LayoutCache:
-    """One BatchLayout per `n_nodes` tensor (identity + version), so the per-layer calls of one forward and
-    repeated forwards over the same batch do the bookkeeping (and its host sync) once."""
-
-    def __init__(self, capacity=16):
-        self.capacity = capacity
-        self.entries = OrderedDict()
+class _LayoutCache(TensorCache):
+    """One BatchLayout per `n_nodes` tensor and device, so the per-layer calls of one forward and repeated forwards over
+    the same batch do the bookkeeping (and its host sync) once."""
 
     def get(self, n_nodes, device):
         if not torch.is_tensor(n_nodes):
             n_nodes = torch.as_tensor(n_nodes)
             return BatchLayout(n_nodes, device)
-        key = (id(n_nodes), n_nodes.data_ptr(), tuple(n_nodes.shape), tensor_version(n_nodes), str(device))
-        hit = self.entries.get(key)
-        if hit is not None:
-            ref, lay = hit
-            if ref() is n_nodes:
-                self.entries.move_to_end(key)
-                return lay
-            del self.entries[key]
-        lay = BatchLayout(n_nodes, device)
-        self.entries[key] = (weakref.ref(n_nodes), lay)
-        while len(self.entries) > self.capacity:
-            self.entries.popitem(last=False)
+        extras = (str(device),)
+        lay = self.lookup((n_nodes,), extras)
+        if lay is MISS:
+            lay = self.insert((n_nodes,), extras, BatchLayout(n_nodes, device))
         return lay
 
-    def clear(self):
-        self.entries.clear()
 
-
-layout_cache = _LayoutCache()
+layout_cache = _LayoutCache(16, unversioned=True)
 
 
 def _check_batch(qs, ks, vs, layout):

@@ -23,12 +23,11 @@ after them, as for the other caches.
 from __future__ import annotations
 
 import copy
-import weakref
-from collections import OrderedDict
 
 import torch
 
 from . import ops
+from .tensor_cache import MISS, TensorCache
 
 # Tests may point this at torch.device("cpu") to run the staging logic (twin refresh, operand cache, gradient routing)
 # on the host-side test backend; the product leaves it None (= the current HIP device).
@@ -54,39 +53,23 @@ def staging_device(module, tensors):
     return torch.device("cuda", torch.cuda.current_device())
 
 
-class _OperandCache:
-    """Device copies of host operands (x, edge_index, edge_weight), one per host tensor: keyed on identity + data_ptr +
-    shape + version and checked against a weak reference, like the CSR cache.  The device edge_index has to be the SAME
-    tensor from call to call or every evaluation would rebuild the CSR and the sliced format."""
-
-    def __init__(self, capacity=6):
-        self.capacity, self.entries = capacity, OrderedDict()
+class _OperandCache(TensorCache):
+    """Device copies of host operands (x, edge_index, edge_weight), one per host tensor and target device.  The device
+    edge_index has to be the SAME tensor from call to call or every evaluation would rebuild the CSR and the sliced format."""
 
     def get(self, t, dev):
         if t is None or not torch.is_tensor(t):
             return t
-        ver = ops.tensor_version(t)
-        key = (id(t), t.data_ptr(), tuple(t.shape), t.dtype, ver, str(dev))
         # on EVERY call: the device copy of a freed host tensor (a full-graph x can be hundreds of MB) goes at once, not at
         # the next miss
-        for k in [k for k, v in self.entries.items() if v[0]() is None]:
-            del self.entries[k]
-        hit = self.entries.get(key)
-        if ver >= 0 and hit is not None and hit[0]() is t:
-            self.entries.move_to_end(key)
-            return hit[1]
-        d = t.detach().to(dev)
-        if ver >= 0:
-            self.entries[key] = (weakref.ref(t), d)
-            while len(self.entries) > self.capacity:
-                self.entries.popitem(last=False)
+        self.purge()
+        d = self.lookup((t,), (str(dev),))
+        if d is MISS:
+            d = self.insert((t,), (str(dev),), t.detach().to(dev))
         return d
 
-    def clear(self):
-        self.entries.clear()
 
-
-operands = _OperandCache()
+operands = _OperandCache(6)
 
 _FLAGS = ("training", "dropout", "use_bn", "residual", "alpha", "auto_graph")
 _CONV_FLAGS = ("training", "kernel", "use_graph", "use_weight", "graph_weight", "use_source", "num_heads", "out_channels")

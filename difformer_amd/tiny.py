@@ -20,12 +20,12 @@ import ctypes
 import math
 import os
 import weakref
-from collections import OrderedDict
 
 import torch
 
 from . import _lib, ops
 from .backend_hip import _stream
+from .tensor_cache import MISS, TensorCache
 
 ENABLED = os.environ.get("DIFFORMER_TINY", "1") != "0"
 MAX_NODES, MAX_HIDDEN, MAX_IN, MAX_OUT, MAX_LAYERS, MAX_EDGES = 4096, 8, 64, 8, 8, 65535
@@ -48,37 +48,19 @@ class TinyGraph:
         return rp, src, val.view(torch.float32), rpt, dst, valt.view(torch.float32)
 
 
-class _GraphCache:
-    """TinyGraph per (edge_index, edge_weight) tensor pair, keyed on identity + version like ops.csr_cache.  A training loop
-    over snapshots makes new tensors per snapshot (main.py:96): every miss is one launch."""
-
-    def __init__(self, capacity=8):
-        self.capacity, self.entries = capacity, OrderedDict()
+class _GraphCache(TensorCache):
+    """TinyGraph per (edge_index, edge_weight) tensor pair and node count.  A training loop over snapshots makes new tensors
+    per snapshot (main.py:96): every miss is one launch.  Tensors made under torch.inference_mode() track no version: their
+    graph is never stored and rebuilt on every call (ops.csr_cache, whose builds cost far more, keys them on -1 instead)."""
 
     def get(self, edge_index, edge_weight, n):
-        # (tensors made under torch.inference_mode() track no version: ops.tensor_version gives -1 and the graph is rebuilt
-        # on every call, as ops.csr_cache does)
-        vi = ops.tensor_version(edge_index)
-        vw = 0 if edge_weight is None else ops.tensor_version(edge_weight)
-        if vi < 0 or vw < 0:
-            return build_graph(edge_index, edge_weight, n)
-        key = (id(edge_index), edge_index.data_ptr(), edge_index.shape[1], vi, n,
-               None if edge_weight is None else (id(edge_weight), edge_weight.data_ptr(), vw))
-        hit = self.entries.get(key)
-        if hit is not None and hit[0]() is edge_index and (edge_weight is None or hit[1]() is edge_weight):
-            self.entries.move_to_end(key)
-            return hit[2]
-        g = build_graph(edge_index, edge_weight, n)
-        self.entries[key] = (weakref.ref(edge_index), None if edge_weight is None else weakref.ref(edge_weight), g)
-        while len(self.entries) > self.capacity:
-            self.entries.popitem(last=False)
+        g = self.lookup((edge_index, edge_weight), (n,))
+        if g is MISS:
+            g = self.insert((edge_index, edge_weight), (n,), build_graph(edge_index, edge_weight, n))
         return g
 
-    def clear(self):
-        self.entries.clear()
 
-
-graphs = _GraphCache()
+graphs = _GraphCache(8)
 stats = {"forward": 0, "backward": 0, "graph_builds": 0}          # calls that took this path (tests assert on them)
 
 # The index check of dif_tiny_graph_build (status[0] != 0: a node id outside [0, n); the entry is filed under node 0) is read

@@ -65,7 +65,7 @@ def _worker(rank, world, port, kernel, n, out_q, heads=2):
             odd = RS(n, rank, world, None, counts=[n - 30, 7, 23])
             ok = ok and bool(torch.equal(odd.all_gather_rows(odd.local_rows(x).contiguous()), x))
         if n >= 64 * world * world and heads > 1:
-            csr = list(ops.csr_cache.entries.values())[-1][2]
+            csr = ops.csr_cache.values()[-1]
             ok = ok and csr.n_blocks == 2 * world and ops._BACKEND.part_calls == {0: 2, 1: 2}     # 2 layers x 2 parts
         if heads == 1 and kernel == "simple":
             # one head: the layers ran in closed form (Gram record all-reduced, source rows all-gathered)

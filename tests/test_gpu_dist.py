@@ -63,7 +63,7 @@ def _worker(rank, world, port, kernel, n, deg, heads, out_q):
         err_x = float((xl.grad - shard.local_rows(ref_x)).abs().max() / ref_x.abs().max())
         torch.cuda.synchronize()
         from difformer_amd import ops
-        sliced = [sl for _, _, csr in ops.csr_cache.entries.values() for sl in csr._sliced.values() if sl is not None]
+        sliced = [sl for csr in ops.csr_cache.values() for sl in csr._sliced.values() if sl is not None]
         splits = max([int(ops.get_backend().lib.dif_sliced_spmm_workspace_bytes(n, shard.n_local, 64 * heads) > 0)] if sliced else [0])
         out_q.put((rank, err_f, err_p, err_x, len(sliced), splits))
     finally:
@@ -122,7 +122,7 @@ def _slice_worker(rank, world, port, n, deg, out_q):
         err = float((local - shard.local_rows(full)).abs().max() / full.abs().max())
         torch.cuda.synchronize()
         # the product ran over ALL rows at the slice width (64 / world columns)
-        widths = sorted({k[2] for _, _, csr in ops.csr_cache.entries.values() for k, sl in csr._sliced.items()
+        widths = sorted({k[2] for csr in ops.csr_cache.values() for k, sl in csr._sliced.items()
                          if sl is not None and k[1] == n})
         out_q.put((rank, err, widths, "dif_sliced_spmm_f32" in launched))
     finally:

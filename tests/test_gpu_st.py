@@ -142,7 +142,7 @@ def _state(dev):
     from difformer_amd import ops
     gc.collect()
     torch.cuda.synchronize()
-    return len(ops.csr_cache.entries), torch.cuda.memory_allocated(dev)
+    return len(ops.csr_cache), torch.cuda.memory_allocated(dev)
 
 
 @pytest.mark.parametrize("kernel,use_graph,n,d,deg,T,dynamic", [

@@ -137,7 +137,7 @@ def test_csr_cache_identity_version_and_eviction(fake_backend):
     assert ops.csr_cache.get(ei, w, 50) is not b          # edge_weight is part of the key
     for _ in range(20):
         ops.csr_cache.get(torch.randint(0, 50, (2, 10)), None, 50)
-    assert len(ops.csr_cache.entries) <= ops.csr_cache.capacity
+    assert len(ops.csr_cache) <= ops.csr_cache.capacity
     # entries whose edge tensors are gone are dropped at the next lookup (a mini-batch loop makes one graph per batch)
     ops.csr_cache.clear()
     keep = torch.randint(0, 50, (2, 40))
@@ -145,7 +145,7 @@ def test_csr_cache_identity_version_and_eviction(fake_backend):
     for _ in range(3):
         ops.csr_cache.get(torch.randint(0, 50, (2, 10)), None, 50)     # temporaries: freed right after the call
     ops.csr_cache.get(keep, None, 50)
-    assert len(ops.csr_cache.entries) == 1
+    assert len(ops.csr_cache) == 1
     wg = torch.rand(40, requires_grad=True)
     # the reference differentiates through the values (difformer.py:73): one GPU returns that gradient
     # (autograd_ops._GcnAggregate), a row-sharded run refuses instead of dropping it silently

@@ -73,14 +73,14 @@ def test_summed_cost_one_backward_then_a_second_epoch(name, fake_backend):
     opt = torch.optim.Adam(model.parameters(), lr=0.01)
     opt.step()
     opt.zero_grad()
-    before = len(ops.csr_cache.entries)
+    before = len(ops.csr_cache)
     cost2, _ = cumulative_epoch(model, snapshots(c), opt)
     assert torch.isfinite(cost2) and float(cost2) != float(cost_tr)
     import gc
     gc.collect()
     cost3, _ = cumulative_epoch(model, snapshots(c), opt)
     gc.collect()
-    assert len(ops.csr_cache.entries) <= max(before, 2 * len(outs))      # entries of freed snapshots do not pile up
+    assert len(ops.csr_cache) <= max(before, 2 * len(outs))      # entries of freed snapshots do not pile up
     assert np.isfinite(evaluate(model, snapshots(c)))
 
 
