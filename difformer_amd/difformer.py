@@ -23,7 +23,7 @@ from . import ops
 from . import autograd_ops as ag
 from . import staging
 from . import tiny
-from .tensor_cache import same_tensors, tensor_key, weak_refs
+from .tensor_cache import remembered, same_tensors, tensor_key, weak_refs
 
 __all__ = ["full_attention_conv", "gcn_conv", "DIFFormerConv", "DIFFormer"]
 
@@ -82,6 +82,28 @@ def gcn_conv(x, edge_index, edge_weight):
     return ag.gcn_aggregate(csr, x, None, 1.0, csr.weight_scale)
 
 
+def mix_scales(graph_weight, use_graph, csr):
+    """(attention scale, graph scale) of the combine, difformer.py:130-136: (1 - w, w) for graph_weight = w > 0, else
+    (1, 1); the graph scale also carries a constant edge_weight (csr.weight_scale: ops._CSRCache.get).  Without a graph
+    the mix does not exist: the attention scale is 1 (and the graph scale multiplies nothing)."""
+    a_s, g_s = (1.0 - graph_weight, float(graph_weight)) if graph_weight > 0 else (1.0, 1.0)
+    if not use_graph:
+        return 1.0, g_s
+    return a_s, g_s * csr.weight_scale
+
+
+_NO_WV = {"weight": None, "bias": None}
+
+
+def _present(params):
+    return [t for t in params if t is not None]
+
+
+def _ln_args(bn):
+    """(weight, bias, eps) of a LayerNorm for the kernels that apply it in their tail; (None, None, 1e-5) without one."""
+    return (bn.weight, bn.bias, bn.eps) if bn is not None else (None, None, 1e-5)
+
+
 class DIFFormerConv(nn.Module):
     """One DIFFormer propagation layer (reference: difformer.py:81-145)."""
 
@@ -101,7 +123,7 @@ class DIFFormerConv(nn.Module):
         self.graph_weight = graph_weight
         self.use_source = use_source
         self.row_shard = None  # set through DIFFormer.set_row_shard for multi-GPU runs
-        self._fused_wb = None  # (key, weight, bias) of the concatenated projections (inference only)
+        self._fused_wb = None  # (key, (weight, bias)) of the concatenated projections (inference only)
         self._wide = None      # (key, ops.WideCoefficients): weight-only factors of the closed form at hidden > 64
         self._narrow = None    # (key, ops.NarrowFactors): weight-only factors of the background coefficient chain
 
@@ -146,24 +168,33 @@ class DIFFormerConv(nn.Module):
         self.invalidate_caches()
         return out
 
+    def _qkv_params(self):
+        """(Wq.weight, Wq.bias, Wk.weight, Wk.bias, Wv.weight | None, Wv.bias | None): the projections as the closed-form
+        kernels take them, None for a missing Wv (use_weight=False).  Plain dict reads, as in DIFFormer._graph_key: this
+        runs in every layer call, and nn.Module.__getattr__ costs about a microsecond per name."""
+        m = self._modules
+        q, k, v = m["Wq"]._parameters, m["Wk"]._parameters, m["Wv"]._parameters if self.use_weight else _NO_WV
+        return (q["weight"], q["bias"], k["weight"], k["bias"], v["weight"], v["bias"])
+
+    def _qkv_list(self):
+        """The parameters that exist, for `ag._needs_grad` and the parameter-version memos."""
+        return _present(self._qkv_params())
+
     # -- projections: one fused GEMM when query and source are the same tensor -----------------
     def _project(self, query_input, source_input):
         H, D = self.num_heads, self.out_channels
         if query_input is source_input:
             mods = [self.Wq, self.Wk] + ([self.Wv] if self.use_weight else [])
-            params = [t for m in mods for t in (m.weight, m.bias)]
+            params = self._qkv_list()
             if ag._needs_grad(*params):
                 w = torch.cat([m.weight for m in mods], dim=0)
                 b = torch.cat([m.bias for m in mods], dim=0)
             else:
                 # inference: the concatenation is rebuilt only when a parameter changes (in-place optimiser steps and
                 # load_state_dict bump _version; .to() replaces the tensors) -- two concat kernels per layer otherwise
-                key = ops.param_key(params)
-                if key is None or self._fused_wb is None or self._fused_wb[0] != key:
-                    with torch.no_grad():
-                        self._fused_wb = (key, torch.cat([m.weight for m in mods], dim=0),
-                                          torch.cat([m.bias for m in mods], dim=0))
-                w, b = self._fused_wb[1], self._fused_wb[2]
+                self._fused_wb = remembered(self._fused_wb, params, lambda: (torch.cat([m.weight for m in mods], dim=0),
+                                                                             torch.cat([m.bias for m in mods], dim=0)))
+                w, b = self._fused_wb[1]
             # [n, (2|3)*H*D]; q/k/v are column slices.  Narrow inputs take the hand-written Linear kernel (one launch,
             # x read once), wide ones the vendor GEMM (autograd_ops.linear decides).
             if w.shape[0] <= 256:
@@ -183,146 +214,166 @@ class DIFFormerConv(nn.Module):
             v = source_input.reshape(-1, 1, D)                # difformer.py:120
         return q, k, v
 
-    def _fusable_projection(self, query_input, source_input):
-        """Projection + simple-kernel reduce in one kernel (csrc/project_reduce.hip)."""
-        if not (self.kernel == 'simple' and self.use_weight and query_input is source_input):
-            return False
-        if source_input.dim() != 2 or source_input.shape[1] > 64 or self.out_channels > 64:
-            return False
-        params = (self.Wq.weight, self.Wq.bias, self.Wk.weight, self.Wk.bias, self.Wv.weight, self.Wv.bias)
-        return not ag._needs_grad(source_input, *params)
+    def _route(self, query_input, source_input, edge_weight, x0, prev, ln_weight, ln_bias, want_qk):
+        """Which kernels run this layer: the single statement of the rule.  Evaluated once per `_layer` call; the methods
+        of the routes rely on it and test none of this again.  x = source_input [n, C], D = out_channels, `wide` = C > 64
+        or D > 64, `training` = a gradient is wanted for x, a projection parameter, x0 or a LayerNorm parameter -- ANY
+        operand of the layer makes it a training call.
 
-    def _closed_form(self, query_input, source_input, prev, want_qk, tail_operands=()):
-        """The whole layer through the Gram-record formulation (csrc/simple_layer.hip): `simple` kernel, one head,
-        query == source, narrow fp32 rows; the residual must mix with the layer input itself.  `tail_operands`: x0 and the
-        LayerNorm parameters -- a gradient wanted for ANY operand of the layer makes it a training call."""
+        Everything but "operator" needs: the `simple` kernel, query_input IS source_input, x two-dimensional, no q / k
+        wanted back (`want_qk`: the dense attention map is made from them) and no gradient for edge_weight
+        (difformer.py:73 is differentiable in it; only the operator path's aggregation has that backward).
+
+        The three closed forms (the whole layer through the Gram record, csrc/simple_layer.hip: q, k, v never exist)
+        need on top of that
+          * one head, float32 or bfloat16 rows, C a multiple of 4 (the kernels read rows as float4);
+          * bfloat16 rows only for the narrow single-GPU layer with bfloat16 parameters (BASELINE config C5): not wide,
+            no row shard, Wq stored as bfloat16;
+          * wide only without a row shard, up to ops.CLOSED_FORM_WIDE_MAX columns (the record is C x C floats), above
+            ops.CLOSED_FORM_WIDE_MIN input columns and with n >= 4 C: the record only pays with many more rows than
+            columns, and from hidden ~256 up (at 128 the two row GEMMs cost what the operator path does; with the
+            one-pass kernel of csrc/simple_layer_wide.hip the threshold is 64 -- see ops.CLOSED_FORM_WIDE_MIN, which
+            DIFFORMER_EXACT_FP32 moves, so it is read here at every call);
+          * C == D without Wv (v = x, difformer.py:120), and with a residual (`prev`): it must be x itself -- the kernel
+            mixes the residual from the rows it already holds;
+          * a backend with `gram`, and with `gram_sym` when wide (a host-side test backend without the record passes:
+            operator path).
+        Then
+          closed_wide       not training, wide: ops.simple_layer_closed_form_wide (Gram-record formulation at the
+                            scripts' widths, hidden 128 / 300 / 400, inference).
+          closed_narrow     not training, not wide: ops.simple_layer_closed_form.
+          closed_train      training, not wide, float32, no row shard (or a world of one), `_CLOSED_FORM_TRAINING` on and a
+                            backend with `simple_reduce`: ag.closed_form_layer, forward and backward through the record
+                            (ag._ClosedFormLayer has that backward up to 64 columns; wide layers train on the operator
+                            path, where a backward through the record was slower: hidden-128 step 5.86 ms against 3.41,
+                            profiles/r06_experiments.md section 5).
+        Otherwise
+          fused_projection  Wv present, C <= 64 and D <= 64, no gradient wanted for x or a projection parameter (x0 and
+                            the LayerNorm live in the tail, which has its own backward): projection + reduce in one
+                            kernel (csrc/project_reduce.hip), ops.project_simple_attention.
+          operator          everything else: q / k / v projections, the attention operator, aggregation with the tail."""
         x = source_input
-        if not (self.kernel == 'simple' and query_input is source_input and self.num_heads == 1 and not want_qk):
-            return False
-        if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16) or x.shape[1] % 4:
-            return False
-        wide = x.shape[1] > 64 or self.out_channels > 64
-        if x.dtype == torch.bfloat16 and (wide or self.row_shard is not None or self.Wq.weight.dtype != torch.bfloat16):
-            return False          # bfloat16 storage: the narrow single-GPU closed form (BASELINE config C5)
-        if wide and (self.row_shard is not None or max(x.shape[1], self.out_channels) > ops.CLOSED_FORM_WIDE_MAX or
-                     x.shape[1] <= ops.CLOSED_FORM_WIDE_MIN or x.shape[0] < 4 * x.shape[1]):
-            return False          # the record is C x C: it only pays with many more rows than columns, and from
-                                  # hidden ~256 up (at 128 the two row GEMMs cost what the operator path does)
-        if not self.use_weight and x.shape[1] != self.out_channels:
-            return False
-        if prev is not None and (prev is not x or x.shape[1] != self.out_channels):
-            return False
-        if not hasattr(ops.get_backend(), "gram") or (wide and not hasattr(ops.get_backend(), "gram_sym")):
-            return False          # (a host-side test backend without the record passes: operator path)
-        params = [self.Wq.weight, self.Wq.bias, self.Wk.weight, self.Wk.bias]
-        if self.use_weight:
-            params += [self.Wv.weight, self.Wv.bias]
-        if not ag._needs_grad(x, *params, *tail_operands):
-            return True
-        # training: the float32 single-GPU closed form has a backward through the record up to 64 columns (ag._ClosedFormLayer)
-        if wide:
-            return False
-        be = ops.get_backend()
-        return (_CLOSED_FORM_TRAINING and x.dtype == torch.float32 and
-                (self.row_shard is None or self.row_shard.world <= 1) and hasattr(be, "simple_reduce"))
+        if (self.kernel != 'simple' or query_input is not source_input or x.dim() != 2 or want_qk or
+                ag._needs_grad(edge_weight)):
+            return "operator"
+        C, D, shard = x.shape[1], self.out_channels, self.row_shard
+        wide = C > 64 or D > 64
+        params = self._qkv_list()
+        if (self.num_heads == 1 and x.dtype in (torch.float32, torch.bfloat16) and C % 4 == 0
+                and not (x.dtype == torch.bfloat16 and (wide or shard is not None or self.Wq.weight.dtype != torch.bfloat16))
+                and not (wide and (shard is not None or max(C, D) > ops.CLOSED_FORM_WIDE_MAX or
+                                   C <= ops.CLOSED_FORM_WIDE_MIN or x.shape[0] < 4 * C))
+                and (self.use_weight or C == D) and (prev is None or (prev is x and C == D))
+                and hasattr(ops.get_backend(), "gram") and (not wide or hasattr(ops.get_backend(), "gram_sym"))):
+            if not ag._needs_grad(x, *params, x0, ln_weight, ln_bias):
+                return "closed_wide" if wide else "closed_narrow"
+            if (not wide and _CLOSED_FORM_TRAINING and x.dtype == torch.float32 and (shard is None or shard.world <= 1)
+                    and hasattr(ops.get_backend(), "simple_reduce")):
+                return "closed_train"
+        if self.use_weight and C <= 64 and D <= 64 and not ag._needs_grad(x, *params):
+            return "fused_projection"
+        return "operator"
 
     def _layer(self, query_input, source_input, edge_index, edge_weight, x0=None, prev=None, alpha=0.5,
                ln_weight=None, ln_bias=None, eps=1e-5, want_qk=False, carry=None):
         """Propagation (:115-136) followed by the tail (:137-140 and, when given, :200-203) -> ([n,D], q, k)."""
-        H = self.num_heads
-        shard = self.row_shard
-        q = k = None
-        w_grad = ag._needs_grad(edge_weight)     # difformer.py:73 is differentiable in edge_weight: operator path then
-        if not w_grad and self._closed_form(query_input, source_input, prev, want_qk, (x0, ln_weight, ln_bias)):
-            if self.use_graph and edge_index is None:
-                raise ValueError("use_graph=True needs an edge_index")
-            x = source_input
-            csr = None
-            if self.use_graph:
-                n_global = shard.n_global if shard is not None else x.shape[0]
-                esz = x.element_size()
-                if ops.slice_sharded(shard, x.shape[1], x.dtype) and x.shape[1] <= 64 and self.out_channels <= 64:
-                    # slice-sharded product: every rank multiplies the WHOLE graph at its C / world columns
-                    csr = ops.csr_cache.get(edge_index, edge_weight, n_global, shard.slice_width(x.shape[1]) * esz, None, esz)
-                else:
-                    csr = ops.csr_cache.get(edge_index, edge_weight, n_global, x.shape[1] * esz, shard, esz)
-            a_s, g_s = (1.0 - self.graph_weight, float(self.graph_weight)) if self.graph_weight > 0 else (1.0, 1.0)
-            if not self.use_graph:
-                a_s = 1.0                                       # difformer.py:130-136: the mix only exists with a graph
-            else:
-                g_s *= csr.weight_scale                         # a constant edge_weight (ops._CSRCache.get)
-            Wv, bv = (self.Wv.weight, self.Wv.bias) if self.use_weight else (None, None)
-            if x.shape[1] > 64 or self.out_channels > 64:          # the scripts' widths (hidden 128 / 300 / 400), inference
-                params = [self.Wq.weight, self.Wq.bias, self.Wk.weight, self.Wk.bias] + ([Wv, bv] if self.use_weight else [])
-                key = ops.param_key(params)
-                if key is None or self._wide is None or self._wide[0] != key:      # weight-only factors: rebuilt when a parameter changes
-                    with torch.no_grad():
-                        self._wide = (key, ops.WideCoefficients(self.Wq.weight, self.Wq.bias, self.Wk.weight, self.Wk.bias,
-                                                                Wv, bv))
-                out = ops.simple_layer_closed_form_wide(x, self._wide[1], Wv, bv, csr, a_s, g_s, x0, prev is not None, alpha,
-                                                        ln_weight, ln_bias, eps)
-                return out, None, None
-            params = (self.Wq.weight, self.Wq.bias, self.Wk.weight, self.Wk.bias, Wv, bv)
-            if ag._needs_grad(x, x0, ln_weight, ln_bias, *params):          # training: forward and backward through the record
-                out = ag.closed_form_layer(x, *params, csr, a_s, g_s, x0, prev is not None, alpha, ln_weight, ln_bias, eps)
-                return out, None, None
-            factors = None
-            if csr is not None and shard is None and x.dtype == torch.float32 and hasattr(ops.get_backend(), "coeffs_bg"):
-                params = [self.Wq.weight, self.Wq.bias, self.Wk.weight, self.Wk.bias] + ([Wv, bv] if self.use_weight else [])
-                key = ops.param_key(params)
-                if key is None or self._narrow is None or self._narrow[0] != key:   # weight-only factors of the background coefficient chain
-                    with torch.no_grad():
-                        self._narrow = (key, ops.NarrowFactors(self.Wq.weight, self.Wq.bias, self.Wk.weight, self.Wk.bias,
-                                                               Wv, bv))
-                factors = self._narrow[1]
-            head = carry.get("head") if carry is not None else None
-            if head is not None and not (head[0].dtype == x.dtype and head[0].shape[0] <= 128 and head[1] is not None):
-                head = None
-            out = ops.simple_layer_closed_form(x, self.Wq.weight, self.Wq.bias, self.Wk.weight, self.Wk.bias, Wv, bv, csr,
-                                               a_s, g_s, x0, prev is not None, alpha, ln_weight, ln_bias, eps, carry=carry,
-                                               shard=shard, factors=factors, head=head)
-            if head is not None:
-                carry["head_done"] = True          # `out` is already the model's logits (difformer.py:208)
-            return out, None, None
-        if not want_qk and not w_grad and self._fusable_projection(query_input, source_input):
-            attn, v = ops.project_simple_attention(source_input, self.Wq.weight, self.Wq.bias, self.Wk.weight,
-                                                   self.Wk.bias, self.Wv.weight, self.Wv.bias, H,
-                                                   self.out_channels, shard, gather_values=self.use_graph)
+        route = self._route(query_input, source_input, edge_weight, x0, prev, ln_weight, ln_bias, want_qk)
+        tail = (x0, prev, alpha, ln_weight, ln_bias, eps)
+        if route == "fused_projection":
+            attn, v = ops.project_simple_attention(source_input, *self._qkv_params(), self.num_heads, self.out_channels,
+                                                   self.row_shard, gather_values=self.use_graph)
+            return self._graph_term_and_tail(attn, v, edge_index, edge_weight, tail), None, None
+        if route == "operator":
+            q, k, attn, v = self._operator(query_input, source_input, edge_index, edge_weight)
+            return self._graph_term_and_tail(attn, v, edge_index, edge_weight, tail), q, k
+        x = source_input
+        csr = self._closed_form_csr(x, edge_index, edge_weight)
+        a_s, g_s = mix_scales(self.graph_weight, self.use_graph, csr)
+        closed = {"closed_wide": self._closed_wide, "closed_train": self._closed_train, "closed_narrow": self._closed_narrow}
+        return closed[route](x, csr, a_s, g_s, tail, carry), None, None
+
+    def _closed_form_csr(self, x, edge_index, edge_weight):
+        """The CSR a closed-form layer aggregates x [n, C] with (None without a graph)."""
+        if not self.use_graph:
+            return None
+        if edge_index is None:
+            raise ValueError("use_graph=True needs an edge_index")
+        shard, esz = self.row_shard, x.element_size()
+        n_global = shard.n_global if shard is not None else x.shape[0]
+        if ops.slice_sharded(shard, x.shape[1], x.dtype) and x.shape[1] <= 64 and self.out_channels <= 64:
+            # slice-sharded product: every rank multiplies the WHOLE graph at its C / world columns
+            return ops.csr_cache.get(edge_index, edge_weight, n_global, shard.slice_width(x.shape[1]) * esz, None, esz)
+        return ops.csr_cache.get(edge_index, edge_weight, n_global, x.shape[1] * esz, shard, esz)
+
+    def _closed_wide(self, x, csr, a_s, g_s, tail, carry):
+        x0, prev, alpha, ln_weight, ln_bias, eps = tail
+        params = self._qkv_params()
+        # weight-only factors: rebuilt when a parameter changes
+        self._wide = remembered(self._wide, _present(params), lambda: ops.WideCoefficients(*params))
+        return ops.simple_layer_closed_form_wide(x, self._wide[1], params[4], params[5], csr, a_s, g_s, x0, prev is not None,
+                                                 alpha, ln_weight, ln_bias, eps)
+
+    def _closed_train(self, x, csr, a_s, g_s, tail, carry):
+        x0, prev, alpha, ln_weight, ln_bias, eps = tail
+        return ag.closed_form_layer(x, *self._qkv_params(), csr, a_s, g_s, x0, prev is not None, alpha, ln_weight, ln_bias, eps)
+
+    def _closed_narrow(self, x, csr, a_s, g_s, tail, carry):
+        x0, prev, alpha, ln_weight, ln_bias, eps = tail
+        params = self._qkv_params()
+        factors = None
+        # (`coeffs_bg` is no route condition: it says whether the factors of the background chain are worth keeping;
+        # ops.simple_layer_closed_form decides whether the chain runs)
+        if csr is not None and self.row_shard is None and x.dtype == torch.float32 and hasattr(ops.get_backend(), "coeffs_bg"):
+            self._narrow = remembered(self._narrow, _present(params), lambda: ops.NarrowFactors(*params))
+            factors = self._narrow[1]
+        head = carry.head if carry is not None else None
+        if head is not None and not (head[0].dtype == x.dtype and head[0].shape[0] <= 128 and head[1] is not None):
+            head = None
+        out = ops.simple_layer_closed_form(x, *params, csr, a_s, g_s, x0, prev is not None, alpha, ln_weight, ln_bias, eps,
+                                           carry=carry, shard=self.row_shard, factors=factors, head=head)
+        if head is not None:
+            carry.head_done = True             # `out` is already the model's logits (difformer.py:208)
+        return out
+
+    def _operator(self, query_input, source_input, edge_index, edge_weight):
+        """q / k / v projections and the attention operator -> (q, k, attn, v)."""
+        H, shard = self.num_heads, self.row_shard
+        q, k, v = self._project(query_input, source_input)
+        v_att = v if v.shape[1] == H else v.expand(-1, H, -1).contiguous()
+        if self.kernel == 'simple':
+            attn = ag.simple_attention(q, k, v_att, shard)
+        elif self.kernel == 'sigmoid':
+            attn = ag.sigmoid_attention(q, k, v_att, shard)
         else:
-            q, k, v = self._project(query_input, source_input)
-            v_att = v if v.shape[1] == H else v.expand(-1, H, -1).contiguous()
-            if self.kernel == 'simple':
-                attn = ag.simple_attention(q, k, v_att, shard)
-            elif self.kernel == 'sigmoid':
-                attn = ag.sigmoid_attention(q, k, v_att, shard)
-            else:
-                raise ValueError(f"unknown attention kernel {self.kernel!r}")
-            if (self.use_graph and not v.is_contiguous() and v.shape[0] >= 65536 and edge_index is not None and
-                    edge_index.shape[1] >= 32 * v.shape[0] and
-                    ops.sliced_tiling(v.shape[0], v.shape[1] * v.shape[2], edge_index.shape[1], edge_weight, shard, v.element_size()) is None):
-                v = v.contiguous()   # the blocked SpMM gathers whole rows: contiguous rows are ~8 % faster on big dense
-                                     # graphs; small or sparse graphs (a Pokec batch: 18 us of copy for a 55-us product)
-                                     # take the strided view as it is (every kernel has a leading dimension)
+            raise ValueError(f"unknown attention kernel {self.kernel!r}")
+        if (self.use_graph and not v.is_contiguous() and v.shape[0] >= 65536 and edge_index is not None and
+                edge_index.shape[1] >= 32 * v.shape[0] and
+                ops.sliced_tiling(v.shape[0], v.shape[1] * v.shape[2], edge_index.shape[1], edge_weight, shard, v.element_size()) is None):
+            v = v.contiguous()   # the blocked SpMM gathers whole rows: contiguous rows are ~8 % faster on big dense
+                                 # graphs; small or sparse graphs (a Pokec batch: 18 us of copy for a 55-us product)
+                                 # take the strided view as it is (every kernel has a leading dimension)
+        return q, k, attn, v
+
+    def _graph_term_and_tail(self, attn, v, edge_index, edge_weight, tail):
+        """What follows the attention on the fused_projection and operator routes: mix with the aggregated values
+        (:130-136), then the tail."""
+        H, shard = self.num_heads, self.row_shard
+        x0, prev, alpha, ln_weight, ln_bias, eps = tail
         if not self.use_graph:
             if isinstance(attn, ops.LazyAttention):
                 attn = attn.materialize()
-            return ag.layer_tail(attn, x0, prev, alpha, ln_weight, ln_bias, eps), q, k
+            return ag.layer_tail(attn, x0, prev, alpha, ln_weight, ln_bias, eps)
         if edge_index is None:
             raise ValueError("use_graph=True needs an edge_index")
         n_global = shard.n_global if shard is not None else v.shape[0]
         esize = (v.local if isinstance(v, ops.GatheredRows) else v).element_size()
         csr = ops.csr_cache.get(edge_index, edge_weight, n_global, v.shape[1] * v.shape[2] * esize, shard, esize)
-        if self.graph_weight > 0:                              # difformer.py:130-132
-            a_s, g_s = 1.0 - self.graph_weight, float(self.graph_weight)
-        else:                                                  # difformer.py:134
-            a_s, g_s = 1.0, 1.0
-        g_s *= csr.weight_scale                                # a constant edge_weight (ops._CSRCache.get)
+        a_s, g_s = mix_scales(self.graph_weight, True, csr)
         if v.shape[1] == H:
-            out = ag.gcn_aggregate_tail(csr, v, attn, a_s, g_s, shard, x0, prev, alpha, ln_weight, ln_bias, eps)
-        else:  # use_weight=False with several heads: the [n,1,D] aggregate broadcasts over heads
-            conv = a_s * attn + g_s * ag.gcn_aggregate(csr, v, None, 1.0, 1.0, shard)
-            out = ag.layer_tail(conv, x0, prev, alpha, ln_weight, ln_bias, eps)
-        return out, q, k
+            return ag.gcn_aggregate_tail(csr, v, attn, a_s, g_s, shard, x0, prev, alpha, ln_weight, ln_bias, eps)
+        # use_weight=False with several heads: the [n,1,D] aggregate broadcasts over heads
+        conv = a_s * attn + g_s * ag.gcn_aggregate(csr, v, None, 1.0, 1.0, shard)
+        return ag.layer_tail(conv, x0, prev, alpha, ln_weight, ln_bias, eps)
 
     def forward(self, query_input, source_input, edge_index=None, edge_weight=None, x_0=None, output_attn=False):
         out, q, k = self._layer(query_input, source_input, edge_index, edge_weight,
@@ -413,8 +464,7 @@ class DIFFormer(nn.Module):
 
     def _input_layer(self, x, training):
         bn = self.bns[0] if self.use_bn else None                     # :188-191 in one kernel
-        x = ag.linear(x, self.fcs[0].weight, self.fcs[0].bias, bn.weight if bn is not None else None,
-                      bn.bias if bn is not None else None, bn.eps if bn is not None else 1e-5, relu=True)
+        x = ag.linear(x, self.fcs[0].weight, self.fcs[0].bias, *_ln_args(bn), relu=True)
         return F.dropout(x, p=self.dropout, training=training)
 
     def _input_with_products(self, x, edge_index, edge_weight, conv0):
@@ -433,10 +483,7 @@ class DIFFormer(nn.Module):
         be = ops.get_backend()
         if not hasattr(be, "input_gram"):
             return None
-        params = [fc.weight, fc.bias, bn.weight, bn.bias, conv0.Wq.weight, conv0.Wq.bias, conv0.Wk.weight, conv0.Wk.bias]
-        if conv0.use_weight:
-            params += [conv0.Wv.weight, conv0.Wv.bias]
-        if ag._needs_grad(x, *params):
+        if ag._needs_grad(x, fc.weight, fc.bias, bn.weight, bn.bias, *conv0._qkv_list()):
             return None
         csr = ops.csr_cache.get(edge_index, None, x.shape[0], hidden * 4)
         sl = csr.sliced(0, x.shape[0], hidden) if x.shape[0] == csr.num_nodes else None
@@ -556,31 +603,29 @@ class DIFFormer(nn.Module):
         if mix is not None:
             x, edge_index = x[mix.perm], mix.edge_index
         # closed-form layers write the slice-major copy of their output (the next layer's SpMM operand) from their registers
-        carry = {}
+        carry = ops.LayerChain()
         first = self._input_with_products(x, edge_index, edge_weight, conv0)
         if first is not None:                                  # :188-192 and the first layer's Gram record / SpMM operand
-            x, carry["products"] = first
+            x, carry.products = first
         else:
             x = self._input_layer(x, self.training)            # difformer.py:188-192
         layer_.append(x)
         for i, conv in enumerate(self.convs):
             bn = self.bns[i + 1] if self.use_bn else None
-            carry["want_next"] = (not self.training) and i + 1 < len(self.convs)
+            carry.want_next = (not self.training) and i + 1 < len(self.convs)
             # the last closed-form layer applies the output Linear (:208) to its rows in the same pass (inference)
             last = i + 1 == len(self.convs)
             fc = self.fcs[-1]
-            carry["head"] = (fc.weight, fc.bias) if (last and not self.training and not ops.EXACT_FP32 and
-                                                     not ag._needs_grad(x, fc.weight, fc.bias)) else None
+            carry.head = (fc.weight, fc.bias) if (last and not self.training and not ops.EXACT_FP32 and
+                                                  not ag._needs_grad(x, fc.weight, fc.bias)) else None
             # head mean, + layer_[0] (use_source), alpha-residual, LayerNorm ride in the last kernel of the
             # layer (:137-140, :200-203)
             x, _, _ = conv._layer(x, x, edge_index, edge_weight, layer_[0] if conv.use_source else None,
-                                  layer_[i] if self.residual else None, self.alpha,
-                                  bn.weight if bn is not None else None, bn.bias if bn is not None else None,
-                                  bn.eps if bn is not None else 1e-5, carry=carry)
+                                  layer_[i] if self.residual else None, self.alpha, *_ln_args(bn), carry=carry)
             if self.training:
                 x = F.dropout(x, p=self.dropout, training=True)
             layer_.append(x)
-        out = x if carry.get("head_done") else ag.linear(x, self.fcs[-1].weight, self.fcs[-1].bias)   # :208
+        out = x if carry.head_done else ag.linear(x, self.fcs[-1].weight, self.fcs[-1].bias)   # :208
         return out[mix.inv] if mix is not None else out
 
     def get_attentions(self, x):
@@ -598,8 +643,6 @@ class DIFFormer(nn.Module):
             v_att = v if v.shape[1] == conv.num_heads else v.expand(-1, conv.num_heads, -1).contiguous()
             c = full_attention_conv(q, k, v_att, conv.kernel)
             bn = self.bns[i + 1] if self.use_bn else None
-            x = ag.layer_tail(c, None, layer_[i] if self.residual else None, self.alpha,
-                              bn.weight if bn is not None else None, bn.bias if bn is not None else None,
-                              bn.eps if bn is not None else 1e-5)
+            x = ag.layer_tail(c, None, layer_[i] if self.residual else None, self.alpha, *_ln_args(bn))
             layer_.append(x)
         return torch.stack(attentions, dim=0)

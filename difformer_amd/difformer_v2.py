@@ -15,7 +15,8 @@ import torch.nn.functional as F
 from . import ops
 from . import autograd_ops as ag
 from . import staging
-from .difformer import gcn_conv
+from .difformer import _ln_args, gcn_conv, mix_scales
+from .tensor_cache import remembered
 
 __all__ = ["make_batch_mask", "make_batch", "to_pad", "gcn_conv", "TransConv", "DIFFormer_v2"]
 
@@ -57,12 +58,12 @@ class TransConv(nn.Module):
         self.use_graph = use_graph
         self.use_weight = use_weight
         self.graph_weight = graph_weight
+        self._cat = None       # (key, (weight, bias)) of the concatenated projections (inference only)
 
     def __getstate__(self):
         state = super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__.copy()
         state = dict(state)
-        for k in ("_cat_key", "_cat_w", "_cat_b"):
-            state.pop(k, None)
+        state.update(_cat=None)
         return state
 
     def reset_parameters(self):
@@ -74,7 +75,7 @@ class TransConv(nn.Module):
     def invalidate_caches(self):
         """Drop the cached concatenation of the projections (needed after parameter writes through `.data`, which do not
         bump the version counter the cache is keyed on)."""
-        self._cat_key = None
+        self._cat = None
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
@@ -92,12 +93,10 @@ class TransConv(nn.Module):
         H, D = self.num_heads, self.out_channels
         params = (self.Wq.weight, self.Wq.bias, self.Wk.weight, self.Wk.bias, self.Wv.weight, self.Wv.bias)
         if query_input is source_input and source_input.shape[1] <= 64 and not ag._needs_grad(source_input, *params):
-            key = ops.param_key(params)
-            if key is None or getattr(self, "_cat_key", None) != key:
-                self._cat_w = torch.cat([self.Wq.weight, self.Wk.weight, self.Wv.weight], dim=0).detach().contiguous()
-                self._cat_b = torch.cat([self.Wq.bias, self.Wk.bias, self.Wv.bias], dim=0).detach().contiguous()
-                self._cat_key = key
-            qkv = ops.linear(source_input, self._cat_w, self._cat_b)
+            self._cat = remembered(self._cat, params, lambda: (
+                torch.cat([self.Wq.weight, self.Wk.weight, self.Wv.weight], dim=0).contiguous(),
+                torch.cat([self.Wq.bias, self.Wk.bias, self.Wv.bias], dim=0).contiguous()))
+            qkv = ops.linear(source_input, *self._cat[1])
             return (qkv[:, : H * D].reshape(-1, H, D), qkv[:, H * D: 2 * H * D].reshape(-1, H, D),
                     qkv[:, 2 * H * D:].reshape(-1, H, D))
         return (ag.linear(query_input, self.Wq.weight, self.Wq.bias).reshape(-1, H, D),
@@ -123,11 +122,7 @@ class TransConv(nn.Module):
         if edge_index is None:
             raise ValueError("use_graph=True needs an edge_index")
         csr = ops.csr_cache.get(edge_index, edge_weight, v.shape[0], H * D * v.element_size(), elem_size=v.element_size())
-        if self.graph_weight > 0:                                                        # :151-152
-            a_s, g_s = 1.0 - self.graph_weight, float(self.graph_weight)
-        else:                                                                            # :154
-            a_s, g_s = 1.0, 1.0
-        g_s *= csr.weight_scale                                                          # a constant edge_weight
+        a_s, g_s = mix_scales(self.graph_weight, True, csr)                              # :151-154
         return ag.gcn_aggregate_tail(csr, v, attn, a_s, g_s, None, None, prev, alpha, ln_weight, ln_bias, eps, relu)
 
     def forward(self, query_input, source_input, n_nodes, edge_index=None, edge_weight=None):
@@ -182,13 +177,12 @@ class DIFFormer_v2(nn.Module):
             return staging.staged_forward(self, dev, lambda m, *a: m.forward(*a), x, edge_index, n_nodes)
         layer_ = []
         bn = self.bns[0] if self.use_bn else None                                        # :197-200 in one kernel
-        x = ag.linear(x, self.fcs[0].weight, self.fcs[0].bias, bn.weight if bn is not None else None,
-                      bn.bias if bn is not None else None, bn.eps if bn is not None else 1e-5, relu=True)
+        x = ag.linear(x, self.fcs[0].weight, self.fcs[0].bias, *_ln_args(bn), relu=True)
         x = F.dropout(x, p=self.dropout, training=self.training)                         # :201
         layer_.append(x)
         for i, conv in enumerate(self.convs):
             bn = self.bns[i + 1] if self.use_bn else None
-            lnw, lnb, eps = (bn.weight, bn.bias, bn.eps) if bn is not None else (None, None, 1e-5)
+            lnw, lnb, eps = _ln_args(bn)
             prev = layer_[i] if self.residual else None
             if self.training and self.dropout > 0:
                 # :212-217: residual -> norm -> dropout -> ReLU; dropout sits between norm and ReLU

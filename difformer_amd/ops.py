@@ -713,6 +713,41 @@ def slice_sharded(shard, C, dtype=torch.float32):
             dtype == torch.float32 and shard.slice_width(C) > 0)
 
 
+class LayerChain:
+    """What the model loop and the closed-form layers of ONE forward hand each other (the `carry` argument; single GPU).
+        want_next  in.   Set by the model loop (DIFFormer._forward_eager) before every layer: another layer follows over
+                         the same graph, so the layer kernel may also write the slice-major pre-scaled copy of its output
+                         (the next layer's SpMM operand) from its registers.  Read by simple_layer_closed_form.
+        head       in.   Set by the model loop before every layer: (weight, bias) of the model's output Linear when this is
+                         the last layer and it may apply the Linear in its own pass, else None.  Read by
+                         DIFFormerConv._closed_narrow, which hands the pair on as `head=` if the kernel takes it.
+        products   layer -> layer.  dict(x, sl, record, ys): what is already known about the rows `x` -- their Gram record
+                         and / or their slice-major copy `ys` for the sliced format `sl`.  Left by
+                         DIFFormer._input_with_products and by a layer kernel asked through `want_next`; consumed by the
+                         next simple_layer_closed_form, which clears it whether it could use it or not.
+        head_done  out.  Set by DIFFormerConv._closed_narrow once `head` was applied: the layer's output is the model's
+                         logits already.  Read by the model loop after the last layer."""
+
+    def __init__(self, want_next=False, head=None, products=None):
+        self.want_next, self.head, self.products, self.head_done = want_next, head, products, False
+
+
+def _simple_layer_kernel(be, x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
+                         next_operand=None, head=None, gather=None):
+    """The layer kernel of the closed form: the one be.simple_layer call.  Optional: next_operand = (rowptr, plan) -> the
+    kernel also returns the slice-major copy of its output; head = (weight, bias) of the model's output Linear -> logits;
+    gather = (rowptr, src, val) -> the kernel aggregates by itself.  Only the ones that are set are passed, so a stand-in
+    backend with a narrower signature keeps working."""
+    optional = {}
+    if next_operand is not None:
+        optional["next_rowptr"], optional["next_plan"] = next_operand
+    if head is not None:
+        optional["head"] = head
+    if gather is not None:
+        optional["gather"] = gather
+    return be.simple_layer(x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu, **optional)
+
+
 def _closed_form_slice_sharded(be, x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_scale, x0, residual, alpha, ln_weight,
                                ln_bias, eps, relu, shard, head):
     """The closed-form layer on a row shard with the aggregation split by FEATURE SLICES: this rank multiplies all
@@ -732,8 +767,81 @@ def _closed_form_slice_sharded(be, x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, g
     rs = None
     if Wv is not None:
         rs = csr.row_sums()[shard.row_begin: shard.row_begin + n]
-    return be.simple_layer(x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
-                           **({"head": head} if head is not None else {}))
+    return _simple_layer_kernel(be, x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
+                                head=head)
+
+
+def _record_and_coeffs(be, x, proj, csr, sl, have, shard, factors, attn_scale):
+    """Stage a of simple_layer_closed_form: where the Gram record and the coefficients come from.
+    have = the carried products of x (LayerChain.products) or None; proj = (Wq, bq, Wk, bk, Wv, bv) in float32.
+    -> (record, ys, coef, side): ys = the slice-major copy of x for `sl` if one exists now, else None; side = None, or
+    (enqueue, join) when the coefficients come from the background chain -- then coef is None until `enqueue()` (to be
+    called right after the product is enqueued) has returned them and `join(coef)` has made the main stream wait."""
+    n, C = x.shape
+    D = proj[0].shape[0]
+    sharded = shard is not None and shard.world > 1
+    n_global = shard.n_global if sharded else n
+    record = have["record"] if have is not None else None
+    ys = have["ys"] if have is not None else None
+    # With the sliced product ahead (0.3 ms that does not need the coefficients) the chain Gram -> coefficients runs as
+    # single-wave background kernels on a second stream, UNDER the product (csrc/side_chain.hip).
+    if (SIDE_CHAIN and factors is not None and sl is not None and not sharded and x.dtype == torch.float32 and
+            C % 4 == 0 and D % 4 == 0 and x.is_cuda and hasattr(be, "coeffs_bg")):
+        if record is None and ys is None:          # first layer: the Gram pass also writes the slice-major copy the product reads
+            record, ys = be.gram(x, csr.rowptr, sl.plan)
+        main, side = torch.cuda.current_stream(x.device), side_stream(x.device)
+        side.wait_stream(main)                     # the chain may start once x (and the record) exist ...
+
+        def enqueue():
+            # ... but is ENQUEUED after the product: its workgroups then take the wave slot the product leaves free on
+            # every CU instead of delaying the product's start
+            with torch.cuda.stream(side):
+                return be.coeffs_bg(None if record is not None else x, record, n_global, factors, C, D, attn_scale)
+
+        def join(coef):                            # the layer kernel needs the coefficients: the side stream joins
+            main.wait_stream(side)
+            coef.record_stream(main)
+        return record, ys, None, (enqueue, join)
+    need_ys = sl is not None and ys is None and not sharded
+    if (record is None and not need_ys and not sharded and x.dtype == torch.float32 and C % 4 == 0 and
+            n <= GRAM_COEFFS_MAX_ROWS and hasattr(be, "gram_coeffs")):
+        # small graphs (node classification/run.sh: Cora ... PubMed): the few partial records of the Gram pass are summed
+        # inside the coefficient kernel -- one launch (and one host call) less in a chain of four dependent ones
+        record, coef = be.gram_coeffs(x, n_global, C, D, *proj, attn_scale)
+        return record, ys, coef, None
+    if record is None:
+        record, ys2 = be.gram(x, csr.rowptr if need_ys else None, sl.plan if need_ys else None)
+        ys = ys2 if need_ys else ys
+    if sharded:
+        shard.all_reduce_sum(record)
+    return record, ys, be.simple_coeffs(record, n_global, C, D, *proj, attn_scale), None
+
+
+def _graph_term(be, x, csr, sl, ys, handle, shard, gcn_scale, want_row_sums, may_gather, after_product):
+    """Stage b of simple_layer_closed_form: how the graph term is produced -> (ax, row sums, gather, late).  Inside the
+    layer kernel (gather = (rowptr, src, val), ax None), by the aggregation kernels (ax = gcn_scale * A_hat x, row sums when
+    there is a Wv whose bias they carry), or not at all (csr None).  handle = the all-gather of x started by the caller
+    (row-sharded) or None; late = what after_product() (stage a's `enqueue`, or None) returned, called as soon as the
+    product is enqueued."""
+    n = x.shape[0]
+    sharded = shard is not None and shard.world > 1
+    row_begin = shard.row_begin if sharded else 0
+    if csr is None:
+        return None, None, None, None
+    if (sl is None and not sharded and may_gather and LAYER_GATHER and csr.n_blocks == 1 and n == csr.num_nodes and
+            0 < csr.nnz <= LAYER_GATHER_MAX_DEGREE * n and hasattr(be, "_simple_layer_gather") and
+            csr.max_degree() <= LAYER_GATHER_MAX_ROW):
+        # a few entries per row: the layer kernel walks the CSR itself, no separate SpMM launch and no `ax` round trip
+        return None, None, (csr.rowptr, csr.src, csr.val), None
+    x_src = handle.wait() if sharded else x
+    ax = _aggregate_rows(be, csr, sl, x_src, row_begin, n, gcn_scale=gcn_scale, ys=ys)
+    late = after_product() if after_product is not None else None
+    rs = None
+    if want_row_sums:
+        rs = csr.row_sums()
+        if sharded:
+            rs = rs[row_begin: row_begin + n]
+    return ax, rs, None, late
 
 
 def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_scale, x0, residual, alpha, ln_weight,
@@ -745,7 +853,7 @@ def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_sca
     Row-sharded: the two exchange steps of SURVEY 8e keep their place -- ONE all-reduce of the 4,160-float Gram record
     (instead of the KtV record) and ONE all-gather of the source rows (x instead of v), started first so that the
     Gram pass and the coefficients run under it.
-    `carry` (dict, optional; single GPU) chains layers over the same graph: with carry["want_next"] the layer kernel also
+    `carry` (LayerChain, optional; single GPU) chains layers over the same graph: with carry.want_next the layer kernel also
     writes the slice-major pre-scaled copy of its output (the next layer's SpMM operand) from its registers; the next layer
     picks it up.
     `keep` (dict, optional; the training forward, autograd_ops._ClosedFormLayer): receives the record, the coefficients, the
@@ -755,83 +863,36 @@ def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_sca
     D = Wq.shape[0]
     # bfloat16 activations (BASELINE config C5): the parameters go in as exact float32 copies, all arithmetic is float32
     Wq, bq, Wk, bk, Wv, bv, ln_weight, ln_bias = (f32_param(t) for t in (Wq, bq, Wk, bk, Wv, bv, ln_weight, ln_bias))
+    tail = (x0, residual, alpha, ln_weight, ln_bias, eps, relu)
     sharded = shard is not None and shard.world > 1
-    n_global, row_begin = (shard.n_global, shard.row_begin) if sharded else (n, 0)
     if sharded and csr is not None and slice_sharded(shard, C, x.dtype):
-        return _closed_form_slice_sharded(be, x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_scale, x0, residual, alpha,
-                                          ln_weight, ln_bias, eps, relu, shard, head)
+        return _closed_form_slice_sharded(be, x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_scale, *tail, shard, head)
     sl = None
     if csr is not None and (sharded or n == csr.num_nodes) and x.dtype == torch.float32:
-        sl = csr.sliced(row_begin, n, C)
+        sl = csr.sliced(shard.row_begin if sharded else 0, n, C)
     handle = shard.all_gather_rows_async(x) if (sharded and csr is not None) else None
-    have = carry.get("products") if (carry is not None and not sharded) else None
+    have = carry.products if (carry is not None and not sharded) else None
     if have is not None and not (have["x"] is x and have["sl"] is sl):
         have = None
-    record = have["record"] if have is not None else None
-    ys = have["ys"] if have is not None else None
-    # With the sliced product ahead (0.3 ms that does not need the coefficients) the chain Gram -> coefficients runs as
-    # single-wave background kernels on a second stream, UNDER the product (csrc/side_chain.hip).
-    background = (SIDE_CHAIN and factors is not None and sl is not None and not sharded and x.dtype == torch.float32 and
-                  C % 4 == 0 and D % 4 == 0 and x.is_cuda and hasattr(be, "coeffs_bg"))
-    coef = join = None
-    if background:
-        if record is None and ys is None:          # first layer: the Gram pass also writes the slice-major copy the product reads
-            record, ys = be.gram(x, csr.rowptr, sl.plan)
-        main, side = torch.cuda.current_stream(x.device), side_stream(x.device)
-        side.wait_stream(main)                     # the chain may start once x (and the record) exist ...
-        join = (main, side)                        # ... but is ENQUEUED after the product (below): its workgroups then take the
-                                                   # wave slot the product leaves free on every CU instead of delaying its start
-    else:
-        need_ys = sl is not None and ys is None and not sharded
-        if (record is None and not need_ys and not sharded and x.dtype == torch.float32 and C % 4 == 0 and
-                n <= GRAM_COEFFS_MAX_ROWS and hasattr(be, "gram_coeffs")):
-            # small graphs (node classification/run.sh: Cora ... PubMed): the few partial records of the Gram pass are summed
-            # inside the coefficient kernel -- one launch (and one host call) less in a chain of four dependent ones
-            record, coef = be.gram_coeffs(x, n_global, C, D, Wq, bq, Wk, bk, Wv, bv, attn_scale)
-        else:
-            if record is None:
-                record, ys2 = be.gram(x, csr.rowptr if need_ys else None, sl.plan if need_ys else None)
-                ys = ys2 if need_ys else ys
-            if sharded:
-                shard.all_reduce_sum(record)
-            coef = be.simple_coeffs(record, n_global, C, D, Wq, bq, Wk, bk, Wv, bv, attn_scale)
-    ax = rs = gather = None
-    want_next = (carry is not None and not sharded and carry.get("want_next", False) and D % 4 == 0 and D == C and
-                 x.dtype == torch.float32)
-    if (csr is not None and sl is None and not sharded and keep is None and LAYER_GATHER and csr.n_blocks == 1 and n == csr.num_nodes and
-            0 < csr.nnz <= LAYER_GATHER_MAX_DEGREE * n and hasattr(be, "_simple_layer_gather") and
-            csr.max_degree() <= LAYER_GATHER_MAX_ROW):
-        # a few entries per row: the layer kernel walks the CSR itself, no separate SpMM launch and no `ax` round trip
-        gather = (csr.rowptr, csr.src, csr.val)
-    elif csr is not None:
-        x_src = handle.wait() if sharded else x
-        ax = _aggregate_rows(be, csr, sl, x_src, row_begin, n, gcn_scale=gcn_scale, ys=ys)
-        if join is not None:                       # (only with the sliced product: `background`)
-            with torch.cuda.stream(join[1]):
-                coef = be.coeffs_bg(None if record is not None else x, record, n_global, factors, C, D, attn_scale)
-        if Wv is not None:
-            rs = csr.row_sums()
-            if sharded:
-                rs = rs[row_begin: row_begin + n]
-    if join is not None:                           # the layer kernel needs the coefficients: the side stream joins
-        join[0].wait_stream(join[1])
-        coef.record_stream(join[0])
+    record, ys, coef, side = _record_and_coeffs(be, x, (Wq, bq, Wk, bk, Wv, bv), csr, sl, have, shard, factors, attn_scale)
+    ax, rs, gather, late = _graph_term(be, x, csr, sl, ys, handle, shard, gcn_scale, Wv is not None, keep is None,
+                                       side[0] if side is not None else None)
+    if side is not None:
+        coef = late
+        side[1](coef)
     if carry is not None:
-        carry["products"] = None
+        carry.products = None
     if keep is not None:
         keep.update(record=record, coef=coef, ax=ax, row_sums=rs)
     if head is not None:                           # last layer: the model's output Linear rides in the same pass -> logits
         head = tuple(f32_param(t) for t in head)   # bfloat16 storage: exact float32 copies, as for the other parameters
-        return be.simple_layer(x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
-                               head=head, gather=gather)
-    if gather is not None:
-        return be.simple_layer(x, coef, D, None, Wv, bv, None, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
-                               gather=gather)
-    if not (want_next and sl is not None):
-        return be.simple_layer(x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu)
-    out, ys2 = be.simple_layer(x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
-                               csr.rowptr, sl.plan)
-    carry["products"] = dict(x=out, sl=sl, record=None, ys=ys2)
+    want_next = (carry is not None and not sharded and carry.want_next and D % 4 == 0 and D == C and
+                 x.dtype == torch.float32 and sl is not None and head is None and gather is None)
+    out = _simple_layer_kernel(be, x, coef, D, ax, Wv, bv, rs, gcn_scale, *tail,
+                               next_operand=(csr.rowptr, sl.plan) if want_next else None, head=head, gather=gather)
+    if want_next:
+        out, ys2 = out
+        carry.products = dict(x=out, sl=sl, record=None, ys=ys2)
     return out
 
 
@@ -961,24 +1022,22 @@ def simple_layer_closed_form_wide(x, coeffs: WideCoefficients, Wv, bv, csr, attn
     x3 = x.reshape(n, 1, C)
     rec = be.gram_sym(x)                                                # [X^T X (upper blocks) | sum x | ...]
     B, bias = be.wide_coeffs(rec, C, n, coeffs.S, coeffs.V, coeffs.P)   # both float64 products + bookkeeping: two launches
+    one_pass = None
     if max(C, D) <= 128 and not EXACT_FP32 and hasattr(be, "simple_layer_wide"):
         # hidden 128 (node classification/run.sh:42-44): both row products, the division, the combine, the residual and the
         # LayerNorm in ONE pass over the rows (csrc/simple_layer_wide.hip) -- no library GEMM, no [n, D + 4] intermediate
-        ax = rs = None
-        if csr is not None:
-            ax = gcn_aggregate(csr, x3, None, 1.0, 1.0).reshape(n, C)
-            rs = csr.row_sums() if Wv is not None else None
-        return be.simple_layer_wide(x, B, bias, D, attn_scale, ax, Wv if csr is not None else None,
-                                    bv if csr is not None else None, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps)
-    if max(C, D) <= XWIDE_MAX and not EXACT_FP32 and hasattr(be, "simple_layer_xwide"):
+        one_pass = be.simple_layer_wide
+    elif max(C, D) <= XWIDE_MAX and not EXACT_FP32 and hasattr(be, "simple_layer_xwide"):
         # hidden 300 / 400 (image and text/run.sh:27): the same one pass with the rows in registers and the weights streamed
         # through LDS (csrc/simple_layer_xwide.hip) instead of a library GEMM per product around a tail pass
+        one_pass = be.simple_layer_xwide
+    if one_pass is not None:
         ax = rs = None
         if csr is not None:
             ax = gcn_aggregate(csr, x3, None, 1.0, 1.0).reshape(n, C)
             rs = csr.row_sums() if Wv is not None else None
-        return be.simple_layer_xwide(x, B, bias, D, attn_scale, ax, Wv if csr is not None else None,
-                                     bv if csr is not None else None, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps)
+        return one_pass(x, B, bias, D, attn_scale, ax, Wv if csr is not None else None, bv if csr is not None else None, rs,
+                        gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps)
     Z = torch.addmm(bias, x, B)                                         # [n, D + 4]: numerator | denominator
     gcn = rs = None
     if csr is not None:

@@ -35,6 +35,19 @@ def param_key(params):
     return tuple(key)
 
 
+def remembered(slot, params, build):
+    """The one memo of a value derived from parameters: `slot` is None or the (key, value) pair this function returned
+    last time, `build()` makes the value.  -> the pair to keep in the slot: the old one while `param_key(params)` is the
+    one it was built under, else a new one, built under torch.no_grad().  An unreadable version (key None) rebuilds on
+    every call.  The pair is immutable: whoever holds an old one (a captured graph) keeps the value it was built with."""
+    key = param_key(params)
+    if key is None or slot is None or slot[0] != key:
+        import torch
+        with torch.no_grad():
+            slot = (key, build())
+    return slot
+
+
 def tensor_key(t):
     """What identifies a tensor and its contents without reading them: (id, data_ptr, shape, dtype, device, version), the
     version -1 when the tensor tracks none; None for None.  All six can come back with a NEW tensor once this one is freed:

@@ -212,16 +212,16 @@ def test_layer_kernel_leaves_the_next_layers_copy(n, deg, c, dev):
         ei = torch.cat([torch.randint(0, n, (2, n * deg), generator=g), torch.arange(n).repeat(2, 1)], dim=1).to(dev)
         csr = ops.csr_cache.get(ei, None, n, c * 4)
         sl = csr.sliced(0, n, c)
-    carry = {"want_next": True}
+    carry = ops.LayerChain(want_next=True)
     out = ops.simple_layer_closed_form(x, p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], csr, 1.0, 1.0, None, True, 0.5,
                                        lw, lb, 1e-5, carry=carry)
     if sl is not None:
-        prod = carry["products"]
+        prod = carry.products
         assert prod is not None and prod["x"] is out and prod["sl"] is sl
         assert prod["record"] is None
         assert torch.equal(prod["ys"], be.gram(out, csr.rowptr, sl.plan)[1])
     else:
-        assert carry["products"] is None           # no sliced product: no copy to leave (and no ys)
+        assert carry.products is None              # no sliced product: no copy to leave (and no ys)
     # and the next layer uses them: same result as a fresh call without the carry
     a = ops.simple_layer_closed_form(out, p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], csr, 1.0, 1.0, None, True, 0.5,
                                      lw, lb, 1e-5, carry=carry)
@@ -414,7 +414,7 @@ def test_layer_kernel_aggregates_sparse_graphs_itself(n, c, dtype, use_weight, g
     be = ops.get_backend()
     xd, eid = x.to(dev), ei.to(dev)
     run = lambda: conv._layer(xd, xd, eid, None, x0.to(dev) if use_source else None, xd, 0.4, lw.to(dev) if ln else None,
-                              lb.to(dev) if ln else None, 1e-5, carry={"head": (cast(hw).to(dev), cast(hb).to(dev))} if head else None)[0]
+                              lb.to(dev) if ln else None, 1e-5, carry=ops.LayerChain(head=(cast(hw).to(dev), cast(hb).to(dev))) if head else None)[0]
     # (a graph seen for the first time keeps the SpMM launch until its longest row is known: the read is not waited for)
     assert ops.csr_cache.get(eid, None, n, c * xd.element_size(), None, xd.element_size()).max_degree() <= ops.LAYER_GATHER_MAX_ROW
     be.kernel_events = {}

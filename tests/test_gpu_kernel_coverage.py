@@ -311,13 +311,13 @@ def test_last_layer_with_the_output_linear_inside_on_the_fp32_chain(dense_graph,
     xd = x.to(dev)
     was = ops.set_exact_fp32(True)
     try:
-        carry = {"head": (hw.to(dev), hb.to(dev))}
+        carry = ops.LayerChain(head=(hw.to(dev), hb.to(dev)))
         with torch.no_grad():
             out, names = _launched(lambda: conv._layer(xd, xd, None if ei is None else ei.to(dev), None, None, xd, 0.4, lw.to(dev),
                                                        lb.to(dev), 1e-5, carry=carry)[0])
     finally:
         ops.set_exact_fp32(was)
-    assert carry.get("head_done") and out.shape == (n, co)
+    assert carry.head_done and out.shape == (n, co)
     p = {"c." + k: v.detach().cpu().double().numpy() for k, v in conv.state_dict().items()}
     cfg = dict(num_heads=1, kernel="simple", use_graph=dense_graph, use_weight=True, graph_weight=-1, use_source=False, hidden_channels=c)
     x64 = x.double().numpy()
