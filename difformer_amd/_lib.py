@@ -7,167 +7,107 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DIFFORMER_HIP_LIB: another build of the SAME ABI (A/B kernel experiments); the default is the in-tree build
 LIB_PATH = os.environ.get("DIFFORMER_HIP_LIB") or os.path.join(_HERE, "lib", "libdifformer_hip.so")
-ABI_VERSION = 3
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_hip.h"))
 
-c_i64, c_int, c_f32, c_vp, c_sz = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+# The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
+# configuration struct; anything else in the header is an error, never a guess.
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+            "double": ctypes.c_double, "size_t": ctypes.c_size_t, "dif_stream_t": ctypes.c_void_p}
+_NAME = r"dif_[a-z0-9_]+"
 
-# name -> (restype, argtypes); mirrors include/difformer_hip.h one to one
-SIGNATURES = {
-    "dif_version": (c_int, []),
-    "dif_set_exact_fp32": (c_int, [c_int]),
-    "dif_last_error": (ctypes.c_char_p, []),
-    "dif_simple_reduced_len": (c_sz, [c_int, c_int, c_int]),
-    "dif_simple_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_int]),
-    "dif_simple_reduce_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int,
-                                      c_vp, c_vp, c_sz, c_vp]),
-    "dif_simple_apply_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
-    "dif_project_reduce_workspace_bytes": (c_sz, [c_i64, c_int, c_int]),
-    "dif_project_reduce_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
-                                       c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
-    "dif_simple_bwd_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_int]),
-    "dif_simple_bwd_prep_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int,
-                                        c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "dif_rowgemm_f32": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_f32, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64,
-                                c_vp, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
-    "dif_sigmoid_workspace_bytes": (c_sz, [c_i64, c_i64, c_int, c_int, c_int]),
-    "dif_sigmoid_attn_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int,
-                                     c_vp, c_i64, c_vp, c_sz, c_vp]),
-    "dif_sigmoid_attn_fwd_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int,
-                                         c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
-    "dif_sigmoid_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_int, c_int, c_int]),
-    "dif_sigmoid_attn_bwd_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64,
-                                         c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_sz, c_vp]),
-    "dif_batched_simple_workspace_bytes": (c_sz, []),
-    "dif_batched_simple_attn_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_i64, c_int, c_int, c_int,
-                                            c_vp, c_i64, c_vp, c_sz, c_vp]),
-    "dif_batched_simple_attn_fwd_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_i64, c_int, c_int, c_int,
-                                                c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
-    "dif_batched_simple_raw_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_i64, c_int, c_int, c_int,
-                                           c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp]),
-    "dif_batched_sigmoid_attn_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int,
-                                             c_int, c_vp, c_i64, c_vp]),
-    "dif_batched_sigmoid_attn_fwd_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int,
-                                                 c_int, c_vp, c_i64, c_vp, c_vp]),
-    "dif_batched_sigmoid_bwd_workspace_bytes": (c_sz, [c_i64, c_int]),
-    "dif_batched_sigmoid_attn_bwd_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
-                                                 c_int, c_int, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
-                                                 c_vp, c_sz, c_vp]),
-    "dif_csr_workspace_bytes": (c_sz, [c_i64, c_i64, c_int]),
-    "dif_csr_build": (c_int, [c_vp, c_i64, c_i64, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
-                              c_vp]),
-    "dif_gcn_spmm_part_scratch_bytes": (c_sz, [c_i64, c_i64, c_int]),
-    "dif_gcn_spmm_part_f32": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_int,
-                                      c_vp, c_i64, c_f32, c_f32, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_f32,
-                                      c_vp, c_vp, c_f32, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp, c_i64, c_vp]),
-    "dif_subgraph_workspace_bytes": (c_sz, [c_i64, c_i64]),
-    "dif_subgraph": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "dif_subgraph_batches_workspace_bytes": (c_sz, [c_i64, c_i64, c_int]),
-    "dif_subgraph_batches_group": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "dif_subgraph_batches_emit": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "dif_graph_prepare_workspace_bytes": (c_sz, [c_i64, c_i64, c_int]),
-    "dif_graph_prepare": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "dif_subgraph_batches_csr_workspace_bytes": (c_sz, [c_i64, c_i64]),
-    "dif_subgraph_batches_csr": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp,
-                                         c_sz, c_vp]),
-    "dif_gcn_spmm_f32": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_int,
-                                 c_vp, c_i64, c_f32, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
-    "dif_gcn_edge_weight_grad_f32": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_f32, c_vp, c_vp]),
-    "dif_gram_workspace_bytes": (c_sz, [c_i64, c_int]),
-    "dif_gram_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "dif_simple_coeffs_len": (c_sz, [c_int, c_int]),
-    "dif_simple_coeffs_f32": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp]),
-    "dif_closed_form_attn_bwd_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
-                                             c_i64, c_vp, c_vp, c_vp]),
-    "dif_closed_form_attn_bwd_groups": (c_int, [c_i64]),
-    "dif_simple_coeffs_bwd_len": (c_sz, [c_int, c_int]),
-    "dif_simple_coeffs_bwd_f32": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp,
-                                          c_vp]),
-    "dif_simple_layer_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp,
-                                     c_i64, c_int, c_f32, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
-    "dif_sliced_plan": (c_int, [c_i64, c_i64, c_int, c_vp]),
-    "dif_sliced_measure": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp,
-                                   c_vp, c_vp, c_vp, c_vp]),
-    "dif_sliced_emit": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
-                                c_vp, c_vp]),
-    "dif_sliced_prescale_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),
-    "dif_sliced_spmm_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp,
-                                    c_i64, c_f32, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
-    "dif_sliced_spmm_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
-    "dif_row_order_workspace_bytes": (c_sz, [c_i64]),
-    "dif_row_order": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "dif_simple_layer_head_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64,
-                                          c_int, c_f32, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64, c_vp]),
-    "dif_gram_bg_workspace_bytes": (c_sz, [c_i64, c_int]),
-    "dif_gram_bg_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "dif_simple_coeffs_bg_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f32, c_vp, c_vp, c_vp]),
-    "dif_gram_sym_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
-    "dif_layer_tail_mix_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_f32, c_vp, c_i64, c_f32, c_vp, c_vp, c_i64, c_int, c_vp, c_i64,
-                                       c_vp, c_i64, c_f32, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp]),
-    "dif_layer_tail_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_f32,
-                                   c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp]),
-    "dif_layer_tail_bwd_workspace_bytes": (c_sz, [c_i64, c_int]),
-    "dif_layer_tail_bwd_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_f32, c_vp, c_vp, c_f32,
-                                       c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
-    "dif_linear_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp]),
-    "dif_input_gram_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp, c_vp, c_vp,
-                                   c_vp, c_vp, c_sz, c_vp]),
-    "dif_simple_layer_wide_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32,
-                                          c_vp, c_i64, c_int, c_f32, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp]),
-    "dif_xwide_packed_bytes": (c_i64, [c_int, c_int]),
-    "dif_xwide_pack_f32": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
-    "dif_simple_layer_xwide_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_f32, c_vp, c_i64, c_vp, c_vp,
-                                           c_f32, c_vp, c_i64, c_int, c_f32, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp]),
-    "dif_gram_coeffs_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp,
-                                    c_sz, c_vp]),
-    "dif_linear_xwide_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp]),
-    "dif_gram128_workspace_bytes": (c_sz, [c_i64, c_int]),
-    "dif_gram128_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
-    "dif_linear_packed_bytes": (c_i64, [c_int]),
-    "dif_linear_pack_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
-    "dif_linear_packed_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp]),
-    "dif_gcn_spmm_tail_f32": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_int,
-                                      c_vp, c_i64, c_f32, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_f32, c_vp, c_vp, c_f32,
-                                      c_int, c_vp, c_i64, c_vp]),
-}
-# bfloat16 storage variants share the argument lists of their float32 twins
-for _n in ("dif_linear", "dif_project_reduce", "dif_simple_reduce", "dif_simple_apply", "dif_layer_tail", "dif_sigmoid_attn"):
-    SIGNATURES[_n + "_bf16"] = SIGNATURES[_n + "_f32"]
-SIGNATURES["dif_gcn_spmm_part_bf16"] = SIGNATURES["dif_gcn_spmm_part_f32"]
-SIGNATURES["dif_simple_layer_head_bf16"] = SIGNATURES["dif_simple_layer_head_f32"]
-SIGNATURES["dif_simple_layer_gather_f32"] = (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32,
-                                                     c_vp, c_i64, c_int, c_f32, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp, c_vp,
-                                                     c_int, c_vp, c_i64, c_vp])
-SIGNATURES["dif_simple_layer_gather_bf16"] = SIGNATURES["dif_simple_layer_gather_f32"]
-SIGNATURES["dif_gram_bf16"] = (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_sz, c_vp])
-SIGNATURES["dif_simple_layer_bf16"] = (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp,
-                                               c_i64, c_int, c_f32, c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp])
-SIGNATURES["dif_gcn_spmm_tail_bf16"] = (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64,
-                                                c_int, c_vp, c_i64, c_f32, c_f32, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_f32,
-                                                c_vp, c_vp, c_f32, c_int, c_vp, c_i64, c_vp])
 
+def _strip(text):
+    """The header without its /* */ comments (#define lines are still there)."""
+    return re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+
+
+def _read_header(path):
+    try:
+        with open(path) as f:
+            return _strip(f.read())
+    except OSError as e:
+        raise ImportError(f"difformer_amd: the C ABI header {path} is missing; the binding is derived from it") from e
+
+
+def _defines(code, pattern):
+    """`#define NAME n` / `#define NAME (n)` for the names that match `pattern` -> {NAME: n}."""
+    found = re.findall(rf"^[ \t]*#[ \t]*define[ \t]+({pattern})[ \t]+\(?(-?\d+)\)?[ \t]*$", code, flags=re.M)
+    if not found:
+        raise ImportError(f"difformer_amd: {HEADER_PATH} defines no integer {pattern}")
+    return {k: int(v) for k, v in found}
+
+
+def _scalar(decl, where):
+    """`[const] type [name]` -> ctypes type; anything that is not a scalar of the table raises."""
+    words = [w for w in decl.split() if w != "const"]
+    if not 1 <= len(words) <= 2 or words[0] not in _SCALARS or not re.fullmatch(r"\w+", words[-1]):
+        raise ImportError(f"difformer_amd: {where}: cannot bind `{' '.join(decl.split())}`")
+    return _SCALARS[words[0]]
+
+
+def _struct_fields(code, name):
+    """`typedef struct { type a, b; ... } name;` -> ctypes _fields_."""
+    m = re.search(rf"typedef\s+struct\s*\{{([^{{}}]*)\}}\s*{name}\s*;", code)
+    if m is None:
+        raise ImportError(f"difformer_amd: {HEADER_PATH} does not declare struct {name}")
+    fields = []
+    for decl in filter(str.strip, m.group(1).split(";")):
+        ctype, *fields_of_type = decl.split(None, 1)
+        names = [f.strip() for f in "".join(fields_of_type).split(",")]
+        if ctype not in _SCALARS or not all(re.fullmatch(r"[A-Za-z_]\w*", f) for f in names):
+            raise ImportError(f"difformer_amd: {name} in {HEADER_PATH}: cannot bind `{' '.join(decl.split())}`")
+        fields += [(f, _SCALARS[ctype]) for f in names]
+    return fields
+
+
+def _prototypes(code):
+    """Every `ret dif_name(params);` of the comment-free header text -> {name: (restype, argtypes)}.  A `dif_name(` that
+    is not such a prototype raises: a skipped function would be called with unchecked arguments."""
+    code = re.sub(r"^[ \t]*#.*$", "", code, flags=re.M)
+    code = re.sub(r"typedef\s+struct\s*\{[^{}]*\}\s*\w+\s*;|extern\s+\"C\"\s*\{", "", code)
+    sigs = {}
+    for stmt in code.split(";")[:-1]:                                # what follows the last ';' is left to the count below
+        if not re.search(rf"{_NAME}\s*\(", stmt):
+            continue
+        m = re.fullmatch(rf"\s*([\w\s*]+?)\s*\b({_NAME})\s*\((.*)\)\s*", stmt, flags=re.S)
+        if m is None:
+            raise ImportError(f"difformer_amd: {HEADER_PATH}: not a prototype: `{' '.join(stmt.split())}`")
+        ret, name, params = m.groups()
+        where = f"{name} in {HEADER_PATH}"
+        restype = ctypes.c_char_p if "".join(ret.split()) == "constchar*" else _scalar(ret, where)
+        argtypes = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            if "*" not in p or re.search(r"[()\[\]]", p):           # by value; arrays and function pointers raise there
+                argtypes.append(_scalar(p, where))
+            elif re.match(r"\s*const\s+dif_tiny_cfg\s*\*", p):
+                argtypes.append(ctypes.POINTER(TinyCfg))
+            else:
+                argtypes.append(ctypes.c_void_p)
+        sigs[name] = (restype, argtypes)
+    names = re.findall(rf"\b({_NAME})\s*\(", code)
+    if len(names) != len(sigs):
+        odd = sorted(n for n in set(names) if n not in sigs or names.count(n) > 1)
+        raise ImportError(f"difformer_amd: {HEADER_PATH} has {len(names)} `dif_*(` for {len(sigs)} prototypes: {', '.join(odd)}")
+    return sigs
+
+
+_code = _read_header(HEADER_PATH)
+ABI_VERSION = _defines(_code, "DIF_ABI_VERSION")["DIF_ABI_VERSION"]
+ERROR_CODES = _defines(_code, r"DIF_E_\w+")                # name -> negative return code of a rejected argument
 
 
 class TinyCfg(ctypes.Structure):
     """dif_tiny_cfg of include/difformer_hip.h."""
-    _fields_ = [(k, ctypes.c_int32) for k in ("n", "in_channels", "hidden", "out_channels", "num_layers", "kernel", "use_bn",
-                                               "use_residual", "use_weight", "use_graph", "use_source", "training")] + \
-               [(k, ctypes.c_float) for k in ("alpha", "attn_scale", "gcn_scale", "dropout", "eps")] + \
-               [("launch_plan", ctypes.c_int32), ("nnz", ctypes.c_int64)]
+    _fields_ = _struct_fields(_code, "dif_tiny_cfg")
 
 
-SIGNATURES["dif_wide_coeffs_f64"] = (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp])
-SIGNATURES["dif_gram_sym_workspace_bytes"] = (c_sz, [c_i64, c_int])
-SIGNATURES["dif_tiny_tape_floats"] = (c_sz, [c_int, c_int, c_int])
-SIGNATURES["dif_tiny_scratch_floats"] = (c_sz, [c_int, c_int, c_int])
-SIGNATURES["dif_tiny_graph_workspace_bytes"] = (c_sz, [c_i64, c_i64])
-SIGNATURES["dif_tiny_graph_build"] = (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp])
-SIGNATURES["dif_tiny_forward_f32"] = (c_int, [ctypes.POINTER(TinyCfg), c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp])
-SIGNATURES["dif_tiny_backward_f32"] = (c_int, [ctypes.POINTER(TinyCfg), c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                               c_vp, c_vp, c_vp])
+# name -> (restype, argtypes): include/difformer_hip.h is the only declaration of the entry points
+SIGNATURES = _prototypes(_code)
 
 _lib = None
 

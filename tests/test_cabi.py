@@ -35,8 +35,96 @@ def test_library_exports_every_declared_symbol(lib):
 
 
 def test_python_binding_covers_the_header_exactly():
+    """The binding's own parser against this file's independent name regex."""
     from difformer_amd import _lib
-    assert sorted(_lib.SIGNATURES) == declared_functions()
+    assert sorted(_lib.SIGNATURES) == declared_functions() and len(_lib.SIGNATURES) == 101
+
+
+def test_derived_signatures_match_hand_written_ones():
+    """A few prototypes transcribed by hand from the header; together they use every entry of the parser's type map."""
+    from ctypes import POINTER, c_char_p, c_float as f32, c_int, c_int64 as i64, c_size_t, c_void_p as vp
+    from difformer_amd import _lib
+    sig = _lib.SIGNATURES
+    assert sig["dif_version"] == (c_int, [])
+    assert sig["dif_last_error"] == (c_char_p, [])
+    assert sig["dif_simple_reduced_len"] == (c_size_t, [c_int, c_int, c_int])
+    assert sig["dif_sliced_spmm_workspace_bytes"] == (i64, [i64, i64, c_int])
+    assert sig["dif_layer_tail_f32"] == (c_int, [vp, i64, i64, c_int, c_int, vp, i64, vp, i64, f32, vp, vp, f32, c_int, vp, i64, vp])
+    assert sig["dif_tiny_forward_f32"] == (c_int, [POINTER(_lib.TinyCfg), vp, i64, vp, vp, vp, vp, vp, vp, vp, vp])
+    assert sig["dif_wide_coeffs_f64"] == (c_int, [vp, c_int, i64, vp, vp, vp, c_int, vp, vp, vp, vp, vp])   # const double*: a pointer
+
+
+def test_derived_struct_version_and_codes():
+    """dif_tiny_cfg: 12 int32, 5 float, 1 int32, then an 8-aligned int64 -- the C layout rules give 68 / 72 / 80."""
+    from difformer_amd import _lib
+    cfg = _lib.TinyCfg
+    i32 = ["n", "in_channels", "hidden", "out_channels", "num_layers", "kernel", "use_bn", "use_residual", "use_weight",
+           "use_graph", "use_source", "training"]
+    f32 = ["alpha", "attn_scale", "gcn_scale", "dropout", "eps"]
+    assert cfg._fields_ == [(k, ctypes.c_int32) for k in i32] + [(k, ctypes.c_float) for k in f32] + \
+        [("launch_plan", ctypes.c_int32), ("nnz", ctypes.c_int64)]
+    assert cfg.launch_plan.offset == 68 and cfg.nnz.offset == 72 and ctypes.sizeof(cfg) == 80
+    assert _lib.ABI_VERSION == 3
+    assert _lib.ERROR_CODES == {"DIF_E_BADARG": -1, "DIF_E_SHAPE": -2, "DIF_E_WORKSPACE": -3, "DIF_E_RANGE": -4}
+
+
+def _parse(text):
+    from difformer_amd import _lib
+    return _lib._prototypes(_lib._strip(text))
+
+
+@pytest.mark.parametrize("params", ["uint8_t flag", "dif_tiny_cfg cfg", "int32_t plan[8]", "void (*done)(int)", "unsigned int n"],
+                         ids=["unknown_type", "struct_by_value", "array", "function_pointer", "two_word_type"])
+def test_parser_refuses_what_it_cannot_bind(params):
+    with pytest.raises(ImportError, match="dif_foo") as e:
+        _parse(f"int dif_ok(int a);\nint dif_foo(const float* x, {params}, dif_stream_t stream);\n")
+    assert params in str(e.value)                                                  # the offending text is named
+
+
+def test_parser_refuses_an_unknown_return_type():
+    for ret in ("void", "float*", "const char"):
+        with pytest.raises(ImportError, match="dif_foo"):
+            _parse(f"{ret} dif_foo(int a);")
+
+
+def test_parser_handles_comments_line_breaks_and_the_preprocessor():
+    from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+    sigs = _parse("""
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define DIF_CALL(x) dif_not_a_function(x)
+/* dif_foo( is described here; so is
+   int dif_ghost(int a); */
+size_t dif_foo(const float* x, int64_t ldx,
+               int n,   /* rows */
+               float
+               scale, void* const* outs,
+               dif_stream_t stream);
+const char *dif_name(void);
+int dif_unnamed(int, const void*);
+#ifdef __cplusplus
+}
+#endif
+""")
+    assert sigs == {"dif_foo": (c_size_t, [c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p]),
+                    "dif_name": (c_char_p, []), "dif_unnamed": (c_int, [c_int, c_void_p])}
+
+
+def test_parser_counts_every_occurrence():
+    """A `dif_*(` that no prototype accounts for is an error, never a skipped function."""
+    for text, named in (("int dif_foo(int a);\nint dif_bar(int b)\n", "dif_bar"),               # no terminating ';'
+                        ("int dif_foo(int a);\nstatic inline int dif_bar(int b) { return b; }\n", "dif_bar"),
+                        ("int dif_foo(int a);\nint dif_foo(int a);\n", "dif_foo"),               # declared twice
+                        ("int dif_foo(int a) dif_bar(int b);\n", "dif_bar")):
+        with pytest.raises(ImportError, match=named):
+            _parse(text)
+
+
+def test_missing_header_fails_loudly(tmp_path):
+    from difformer_amd import _lib
+    with pytest.raises(ImportError, match="nope.h"):
+        _lib._read_header(str(tmp_path / "nope.h"))
 
 
 def test_exact_fp32_switch_is_a_runtime_setting_of_the_library(lib):
