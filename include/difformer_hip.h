@@ -11,6 +11,9 @@
  *   - plain pointers and sizes only; every pointer is DEVICE memory owned by the caller
  *     (row-major, 16-byte aligned, leading dimensions given in ELEMENTS), including all
  *     workspaces -- the library never allocates, frees or synchronises;
+ *   - no entry point reads or writes outside [base, base + rows * ld) of any operand or beyond `workspace_bytes` of a
+ *     workspace, and the contents of outputs and workspaces on entry are unspecified: nothing is assumed to be zero
+ *     (tests/test_gpu_guarded_*.py run every entry point between poisoned guard bands to hold the library to this);
  *   - work is enqueued on the `stream` argument only (a hipStream_t passed as void*; NULL =
  *     the null stream), so every call is stream-ordered and graph-capturable;
  *   - return 0 on success, a negative DIF_E_* code for a rejected argument, or a positive
