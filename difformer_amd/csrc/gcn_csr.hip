@@ -32,51 +32,6 @@ constexpr int kSortRoundsMin = 8;   // small graphs (mini-batches): shorter chun
 constexpr int kRadixBits = 8;
 constexpr int kRadix = 1 << kRadixBits;
 
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-struct Plan {
-    int64_t E, N;
-    int64_t NB, block_rows, n_keys;  // source blocks, nodes per block, N * NB sort keys
-    int rounds;            // 64-key rounds per wave chunk
-    int64_t n_chunks;      // sort chunks (waves)
-    int64_t table_len;     // kRadix * n_chunks
-    int passes;            // radix passes over the destination id
-    size_t off_keys_a, off_keys_b, off_vals_a, off_vals_b, off_deg, off_dinv, off_degc, off_table, off_bsum, total;
-};
-
-Plan make_plan(int64_t E, int64_t N, int64_t NB, int64_t block_rows = 0) {
-    Plan p;
-    p.E = E; p.N = N;
-    p.NB = NB < 1 ? 1 : NB;
-    p.block_rows = block_rows > 0 ? block_rows : (N + p.NB - 1) / p.NB;
-    p.n_keys = N * p.NB;
-    int64_t rounds = (E + 64 * 4096 - 1) / (64 * 4096);     // aim at ~4096 waves
-    if (rounds < kSortRoundsMin) rounds = kSortRoundsMin;
-    if (rounds > kSortRoundsMax) rounds = kSortRoundsMax;
-    p.rounds = static_cast<int>(rounds);
-    const int64_t chunk = 64 * rounds;
-    p.n_chunks = (E + chunk - 1) / chunk;
-    if (p.n_chunks < 1) p.n_chunks = 1;
-    p.table_len = p.n_chunks * kRadix;
-    int bits = 1;
-    while ((int64_t(1) << bits) < p.n_keys) ++bits;
-    p.passes = (bits + kRadixBits - 1) / kRadixBits;
-    const size_t e = static_cast<size_t>(E > 0 ? E : 1);
-    const int64_t scan_n = (p.table_len > p.n_keys + 1) ? p.table_len : (p.n_keys + 1);
-    size_t o = 0;
-    p.off_keys_a = o; o += align256(e * 4);
-    p.off_keys_b = o; o += align256(e * 4);
-    p.off_vals_a = o; o += align256(e * 4);
-    p.off_vals_b = o; o += align256(e * 4);
-    p.off_deg = o;    o += align256(static_cast<size_t>(p.n_keys + 1) * 4);   // per-key counts, then key pointers
-    p.off_dinv = o;   o += align256(static_cast<size_t>(N + 1) * 4);
-    p.off_degc = o;   o += align256(static_cast<size_t>(N + 1) * 4);   // in-degree over `col` (transposed build)
-    p.off_table = o;  o += align256(static_cast<size_t>(p.table_len) * 4);
-    p.off_bsum = o;   o += align256(static_cast<size_t>((scan_n + kScanTile - 1) / kScanTile + 1) * 4);
-    p.total = o;
-    return p;
-}
-
 // ---- sort keys (row it is filed under x source block) and payloads --------------------------------
 // Payload: the edge id when the graph is weighted (the weight is fetched after the sort), otherwise directly the node
 // id the entry will gather -- the sorted payload then IS the CSR `src` array and the fill pass needs no random access
@@ -652,86 +607,236 @@ __global__ __launch_bounds__(256) void prep_emit_kernel(const uint32_t* __restri
     if (blockIdx.x == 0 && threadIdx.x == 0) *out_count = kept + (add_loops ? N : 0);
 }
 
-struct PrepPlan { int rounds; int64_t n, n_chunks, table_len; int passes; size_t off_ka, off_kb, off_va, off_vb, off_keep, off_table, off_bsum, total; };
-PrepPlan make_prep_plan(int64_t E, int64_t N, int undirected) {
-    PrepPlan p;
-    p.n = undirected ? 2 * E : E;
-    int64_t rounds = (p.n + 64 * 4096 - 1) / (64 * 4096);
+// ---- host side: the helpers every entry point below uses -------------------------------------------------------------
+// grid of a grid-stride kernel: `blocks` clamped to [1, 8 per CU]
+unsigned capped_blocks(int64_t blocks) {
+    const int64_t cap = 8 * dif::kCUs;
+    return static_cast<unsigned>(blocks > cap ? cap : blocks < 1 ? 1 : blocks);
+}
+unsigned capped_grid(int64_t n) { return capped_blocks((n + 255) / 256); }   // 256 threads per block
+
+int zero_async(const char* who, void* p, size_t bytes, hipStream_t st) {
+    const hipError_t he = hipMemsetAsync(p, 0, bytes, st);
+    return he == hipSuccess ? 0 : dif::fail(static_cast<int>(he), "%s: memset: %s", who, hipGetErrorString(he));
+}
+
+int check_workspace(const char* who, const void* workspace, size_t have, size_t need) {
+    DIF_REQUIRE(have >= need, DIF_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, have, need);
+    DIF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, DIF_E_BADARG, "%s: workspace must be 256-byte aligned", who);
+    return 0;
+}
+
+// n_batches of the three dif_subgraph_batches_* calls.  The group sort files dropped edges under key 0xffff, which has to
+// sort behind every batch.
+int batch_count(int64_t M, int64_t batch_size, int* n_batches) {
+    const int64_t nb64 = (M + batch_size - 1) / batch_size;
+    DIF_REQUIRE(nb64 < 65535, DIF_E_RANGE, "dif_subgraph_batches: at most 65,534 batches");
+    *n_batches = static_cast<int>(nb64);
+    return 0;
+}
+
+// ---- workspace layout: 256-byte aligned pieces, one after the other --------------------------------------------------
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+struct Arena {
+    size_t o = 0;                                   // bytes taken so far = the total when the layout is complete
+    size_t take(size_t bytes) { const size_t at = o; o += align256(bytes); return at; }
+};
+
+// block sums of exclusive_scan over scan_n values (+ 1: the grand total)
+inline size_t scan_scratch_bytes(int64_t scan_n) { return static_cast<size_t>((scan_n + kScanTile - 1) / kScanTile + 1) * 4; }
+
+template <class T> T* at(char* ws, size_t off) { return reinterpret_cast<T*>(ws + off); }
+template <class T> const T* at(const char* ws, size_t off) { return reinterpret_cast<const T*>(ws + off); }
+
+// ---- the sort: geometry, buffers, the pass loop ----------------------------------------------------------------------
+struct SortGeom {
+    int64_t n;             // (key, payload) pairs
+    int rounds;            // 64-key rounds per wave chunk
+    int64_t n_chunks;      // sort chunks (waves)
+    int64_t table_len;     // kRadix * n_chunks
+    int passes;            // radix passes, kRadixBits of the key each
+};
+
+// passes that order keys in [0, n_keys)
+int key_passes(int64_t n_keys) {
+    int bits = 1;
+    while ((int64_t(1) << bits) < n_keys) ++bits;
+    return (bits + kRadixBits - 1) / kRadixBits;
+}
+
+// rounds = 0: from the item count
+SortGeom sort_geom(int64_t n, int passes, int64_t rounds = 0) {
+    SortGeom g;
+    g.n = n;
+    constexpr int64_t per_round = 64 * 4096;                         // aim at ~4096 waves
+    if (rounds == 0) rounds = (n + per_round - 1) / per_round;
     if (rounds < kSortRoundsMin) rounds = kSortRoundsMin;
     if (rounds > kSortRoundsMax) rounds = kSortRoundsMax;
-    p.rounds = static_cast<int>(rounds);
+    g.rounds = static_cast<int>(rounds);
     const int64_t chunk = 64 * rounds;
-    p.n_chunks = (p.n + chunk - 1) / chunk;
-    if (p.n_chunks < 1) p.n_chunks = 1;
-    p.table_len = p.n_chunks * kRadix;
-    int bits = 1;
-    while ((int64_t(1) << bits) < N) ++bits;
-    p.passes = (bits + kRadixBits - 1) / kRadixBits;
-    const size_t e = static_cast<size_t>(p.n > 0 ? p.n : 1);
-    const int64_t scan_n = p.table_len > p.n + 1 ? p.table_len : p.n + 1;
-    size_t o = 0;
-    p.off_ka = o;    o += align256(e * 4);
-    p.off_kb = o;    o += align256(e * 4);
-    p.off_va = o;    o += align256(e * 4);
-    p.off_vb = o;    o += align256(e * 4);
-    p.off_keep = o;  o += align256((e + 1) * 4);
-    p.off_table = o; o += align256(static_cast<size_t>(p.table_len) * 4);
-    p.off_bsum = o;  o += align256(static_cast<size_t>((scan_n + kScanTile - 1) / kScanTile + 1) * 4);
-    p.total = o;
+    g.n_chunks = (n + chunk - 1) / chunk;
+    if (g.n_chunks < 1) g.n_chunks = 1;
+    g.table_len = g.n_chunks * kRadix;
+    g.passes = passes;
+    return g;
+}
+
+struct SortBufs {
+    uint32_t *kin, *kout;    // keys: what the next pass reads, what it writes
+    uint32_t *vin, *vout;    // payload, likewise
+    int32_t *table, *bsum;   // per-chunk digit counts [table_len] and the scratch of their scan
+};
+
+// g.passes stable passes over the pairs in (b.kin, b.vin), lowest digit first.  Every pass swaps the roles of the two pairs
+// of buffers, so on return b.kin / b.vin hold the sorted keys / payload wherever the last pass left them: in the pair that
+// came in as (kout, vout) after an odd number of passes, in the one that came in as (kin, vin) after an even number.
+int radix_sort(const SortGeom& g, SortBufs& b, hipStream_t st) {
+    const unsigned sort_grid = static_cast<unsigned>((g.n_chunks + kSortWaves - 1) / kSortWaves);
+    for (int pass = 0; pass < g.passes; ++pass) {
+        const int shift = pass * kRadixBits;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin, g.n, shift, g.n_chunks,
+                           g.rounds, b.table);
+        if (int rc = dif::launch_status("radix_hist_kernel")) return rc;
+        if (int rc = exclusive_scan(b.table, g.table_len, b.table, nullptr, b.bsum, st)) return rc;
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin, b.vin, g.n, shift,
+                           g.n_chunks, g.rounds, b.table, b.kout, b.vout);
+        if (int rc = dif::launch_status("radix_scatter_kernel")) return rc;
+        uint32_t* t = b.kin; b.kin = b.kout; b.kout = t;
+        t = b.vin; b.vin = b.vout; b.vout = t;
+    }
+    return 0;
+}
+
+// ---- one plan per entry point: its sort and where its pieces sit in the workspace ------------------------------------
+struct Plan {
+    int64_t E, N;
+    int64_t NB, block_rows, n_keys;  // source blocks, nodes per block, N * NB sort keys
+    SortGeom sort;                   // E entries, passes over the key (destination id x source block)
+    size_t off_ka, off_kb, off_va, off_vb, off_deg, off_dinv, off_degc, off_table, off_bsum, total;
+};
+
+Plan make_plan(int64_t E, int64_t N, int64_t NB, int64_t block_rows = 0) {
+    Plan p;
+    p.E = E; p.N = N;
+    p.NB = NB < 1 ? 1 : NB;
+    p.block_rows = block_rows > 0 ? block_rows : (N + p.NB - 1) / p.NB;
+    p.n_keys = N * p.NB;
+    p.sort = sort_geom(E, key_passes(p.n_keys));
+    const size_t e = static_cast<size_t>(E > 0 ? E : 1);
+    const int64_t scan_n = (p.sort.table_len > p.n_keys + 1) ? p.sort.table_len : (p.n_keys + 1);
+    Arena a;
+    p.off_ka = a.take(e * 4);
+    p.off_kb = a.take(e * 4);
+    p.off_va = a.take(e * 4);
+    p.off_vb = a.take(e * 4);
+    p.off_deg = a.take(static_cast<size_t>(p.n_keys + 1) * 4);   // per-key counts, then key pointers
+    p.off_dinv = a.take(static_cast<size_t>(N + 1) * 4);
+    p.off_degc = a.take(static_cast<size_t>(N + 1) * 4);         // in-degree over `col` (transposed build)
+    p.off_table = a.take(static_cast<size_t>(p.sort.table_len) * 4);
+    p.off_bsum = a.take(scan_scratch_bytes(scan_n));
+    p.total = a.o;
     return p;
 }
 
-struct BatchCsrPlan { int rounds; int64_t n_chunks, table_len; int passes; size_t off_ka, off_kb, off_va, off_vb, off_dinv, off_table, off_bsum, total; };
-BatchCsrPlan make_batch_csr_plan(int64_t kept, int64_t M) {
-    BatchCsrPlan p;
-    int64_t rounds = (kept + 64 * 4096 - 1) / (64 * 4096);
-    if (rounds < kSortRoundsMin) rounds = kSortRoundsMin;
-    if (rounds > kSortRoundsMax) rounds = kSortRoundsMax;
-    p.rounds = static_cast<int>(rounds);
-    const int64_t chunk = 64 * rounds;
-    p.n_chunks = (kept + chunk - 1) / chunk;
-    if (p.n_chunks < 1) p.n_chunks = 1;
-    p.table_len = p.n_chunks * kRadix;
-    int bits = 1;
-    while ((int64_t(1) << bits) < M) ++bits;
-    p.passes = (bits + kRadixBits - 1) / kRadixBits;
-    const size_t e = static_cast<size_t>(kept > 0 ? kept : 1);
-    const int64_t scan_n = p.table_len > M + 1 ? p.table_len : M + 1;
-    size_t o = 0;
-    p.off_ka = o;    o += align256(e * 4);
-    p.off_kb = o;    o += align256(e * 4);
-    p.off_va = o;    o += align256(e * 4);
-    p.off_vb = o;    o += align256(e * 4);
-    p.off_dinv = o;  o += align256(static_cast<size_t>(M + 1) * 4);
-    p.off_table = o; o += align256(static_cast<size_t>(p.table_len) * 4);
-    p.off_bsum = o;  o += align256(static_cast<size_t>((scan_n + kScanTile - 1) / kScanTile + 1) * 4);
-    p.total = o;
+constexpr int kOrderPasses = 3;                     // 24 bits of (2^24 - 1 - degree)
+struct OrderPlan { SortGeom sort; size_t off_ka, off_kb, off_va, off_table, off_bsum, total; };
+OrderPlan make_order_plan(int64_t n) {
+    OrderPlan p;
+    p.sort = sort_geom(n, kOrderPasses, kSortRoundsMin);            // shards are small: short chunks whatever n is
+    const size_t e = static_cast<size_t>(n > 0 ? n : 1);
+    Arena a;
+    p.off_ka = a.take(e * 4);
+    p.off_kb = a.take(e * 4);
+    p.off_va = a.take(e * 4);                       // the second payload buffer is the caller's `order`
+    p.off_table = a.take(static_cast<size_t>(p.sort.table_len) * 4);
+    p.off_bsum = a.take(scan_scratch_bytes(p.sort.table_len));
+    p.total = a.o;
     return p;
 }
 
-struct BatchPlan { int rounds; int64_t n_chunks, table_len; int passes; size_t off_info, off_ka, off_kb, off_va, off_vb, off_table, off_bsum, total; };
+// newid [N] | mask words [ceil(E / 64)] | chunk counts [E / 4,096 + 2] | the scan's block sums | member bitmap [N / 32]
+struct SubPlan { int64_t n_chunks; size_t off_newid, off_mask, off_counts, off_bsum, off_member, total; };
+SubPlan make_sub_plan(int64_t E, int64_t N) {
+    SubPlan p;
+    p.n_chunks = (E + kSubChunk - 1) / kSubChunk;
+    Arena a;
+    p.off_newid = a.take(static_cast<size_t>(N) * 4);
+    p.off_mask = a.take(static_cast<size_t>((E + 63) / 64 + 1) * 8);
+    p.off_counts = a.take(static_cast<size_t>(p.n_chunks + 2) * 4);
+    p.off_bsum = a.take(scan_scratch_bytes(p.n_chunks + 1));
+    p.off_member = a.take(static_cast<size_t>((N + 31) / 32) * 4);
+    p.total = a.o;
+    return p;
+}
+
+struct BatchPlan {
+    SortGeom sort;
+    size_t off_info, off_ka, off_kb, off_va, off_vb, off_table, off_bsum, total;
+    // The grouped edge ids are the payload of the group sort, which starts in (ka, va): radix_sort leaves them in vb after
+    // one pass and back in va after two.  The workspace outlives the call; the emit and CSR phases read them from here.
+    size_t off_grouped() const { return sort.passes % 2 ? off_vb : off_va; }
+};
 BatchPlan make_batch_plan(int64_t E, int64_t N, int n_batches) {
     BatchPlan p;
-    int64_t rounds = (E + 64 * 4096 - 1) / (64 * 4096);
-    if (rounds < kSortRoundsMin) rounds = kSortRoundsMin;
-    if (rounds > kSortRoundsMax) rounds = kSortRoundsMax;
-    p.rounds = static_cast<int>(rounds);
-    const int64_t chunk = 64 * rounds;
-    p.n_chunks = (E + chunk - 1) / chunk;
-    if (p.n_chunks < 1) p.n_chunks = 1;
-    p.table_len = p.n_chunks * kRadix;
-    p.passes = n_batches < 255 ? 1 : 2;
+    // one pass on the low 8 bits of the key while every batch id stays below 255, the low byte of the dropped key 0xffff;
+    // two passes on all 16 bits otherwise
+    p.sort = sort_geom(E, n_batches < 255 ? 1 : 2);
     const size_t e = static_cast<size_t>(E > 0 ? E : 1);
-    size_t o = 0;
-    p.off_info = o;  o += align256(static_cast<size_t>(N) * 4);
-    p.off_ka = o;    o += align256(e * 4);
-    p.off_kb = o;    o += align256(e * 4);
-    p.off_va = o;    o += align256(e * 4);
-    p.off_vb = o;    o += align256(e * 4);
-    p.off_table = o; o += align256(static_cast<size_t>(p.table_len) * 4);
-    p.off_bsum = o;  o += align256(static_cast<size_t>((p.table_len + kScanTile - 1) / kScanTile + 1) * 4);
-    p.total = o;
+    Arena a;
+    p.off_info = a.take(static_cast<size_t>(N) * 4);
+    p.off_ka = a.take(e * 4);
+    p.off_kb = a.take(e * 4);
+    p.off_va = a.take(e * 4);
+    p.off_vb = a.take(e * 4);
+    p.off_table = a.take(static_cast<size_t>(p.sort.table_len) * 4);
+    p.off_bsum = a.take(scan_scratch_bytes(p.sort.table_len));
+    p.total = a.o;
     return p;
+}
+
+struct BatchCsrPlan { SortGeom sort; size_t off_ka, off_kb, off_va, off_vb, off_dinv, off_table, off_bsum, total; };
+BatchCsrPlan make_batch_csr_plan(int64_t kept, int64_t M) {
+    BatchCsrPlan p;
+    p.sort = sort_geom(kept, key_passes(M));        // key = position of the destination in the permutation
+    const size_t e = static_cast<size_t>(kept > 0 ? kept : 1);
+    const int64_t scan_n = p.sort.table_len > M + 1 ? p.sort.table_len : M + 1;
+    Arena a;
+    p.off_ka = a.take(e * 4);
+    p.off_kb = a.take(e * 4);
+    p.off_va = a.take(e * 4);
+    p.off_vb = a.take(e * 4);
+    p.off_dinv = a.take(static_cast<size_t>(M + 1) * 4);
+    p.off_table = a.take(static_cast<size_t>(p.sort.table_len) * 4);
+    p.off_bsum = a.take(scan_scratch_bytes(scan_n));
+    p.total = a.o;
+    return p;
+}
+
+struct PrepPlan { SortGeom sort; size_t off_ka, off_kb, off_va, off_vb, off_keep, off_table, off_bsum, total; };
+PrepPlan make_prep_plan(int64_t E, int64_t N, int undirected) {
+    PrepPlan p;
+    p.sort = sort_geom(undirected ? 2 * E : E, key_passes(N));      // both sorts are on a node id
+    const int64_t n = p.sort.n;
+    const size_t e = static_cast<size_t>(n > 0 ? n : 1);
+    const int64_t scan_n = p.sort.table_len > n + 1 ? p.sort.table_len : n + 1;
+    Arena a;
+    p.off_ka = a.take(e * 4);
+    p.off_kb = a.take(e * 4);
+    p.off_va = a.take(e * 4);
+    p.off_vb = a.take(e * 4);
+    p.off_keep = a.take((e + 1) * 4);
+    p.off_table = a.take(static_cast<size_t>(p.sort.table_len) * 4);
+    p.off_bsum = a.take(scan_scratch_bytes(scan_n));
+    p.total = a.o;
+    return p;
+}
+
+// the two pairs of sort buffers of a plan, the sort reading (ka, va) first
+template <class P>
+SortBufs sort_bufs(char* ws, const P& p) {
+    return SortBufs{at<uint32_t>(ws, p.off_ka), at<uint32_t>(ws, p.off_kb), at<uint32_t>(ws, p.off_va), at<uint32_t>(ws, p.off_vb),
+                    at<int32_t>(ws, p.off_table), at<int32_t>(ws, p.off_bsum)};
 }
 
 }  // namespace
@@ -756,88 +861,40 @@ extern "C" int dif_csr_build(const int64_t* edge_index, int64_t E, int64_t N, co
     DIF_REQUIRE(block_rows >= 0 && (block_rows == 0 || block_rows * n_blocks >= N), DIF_E_BADARG,
                 "dif_csr_build: block_rows * n_blocks must cover N (block_rows = 0: ceil(N / n_blocks))");
     const Plan p = make_plan(E, N, n_blocks, block_rows);
-    DIF_REQUIRE(workspace_bytes >= p.total, DIF_E_WORKSPACE, "dif_csr_build: workspace too small (%zu < %zu)",
-                workspace_bytes, p.total);
-    DIF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, DIF_E_BADARG,
-                "dif_csr_build: workspace must be 256-byte aligned");
+    if (int rc = check_workspace("dif_csr_build", workspace, workspace_bytes, p.total)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
-    uint32_t* keys_a = reinterpret_cast<uint32_t*>(ws + p.off_keys_a);
-    uint32_t* keys_b = reinterpret_cast<uint32_t*>(ws + p.off_keys_b);
-    uint32_t* vals_a = reinterpret_cast<uint32_t*>(ws + p.off_vals_a);
-    uint32_t* vals_b = reinterpret_cast<uint32_t*>(ws + p.off_vals_b);
-    int32_t* kcnt = reinterpret_cast<int32_t*>(ws + p.off_deg);   // per-key counts -> key pointers (in place)
-    float* dinv = reinterpret_cast<float*>(ws + p.off_dinv);
-    int32_t* degc = transpose ? reinterpret_cast<int32_t*>(ws + p.off_degc) : nullptr;
-    int32_t* table = reinterpret_cast<int32_t*>(ws + p.off_table);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + p.off_bsum);
+    SortBufs b = sort_bufs(ws, p);
+    int32_t* kcnt = at<int32_t>(ws, p.off_deg);   // per-key counts -> key pointers (in place)
+    float* dinv = at<float>(ws, p.off_dinv);
+    int32_t* degc = transpose ? at<int32_t>(ws, p.off_degc) : nullptr;
 
-    hipError_t he = hipMemsetAsync(status, 0, 8, st);            // {bad index flag, longest row}
-    if (he == hipSuccess && transpose) he = hipMemsetAsync(degc, 0, static_cast<size_t>(N + 1) * 4, st);
-    if (he != hipSuccess) return dif::fail(static_cast<int>(he), "dif_csr_build: memset: %s", hipGetErrorString(he));
+    if (int rc = zero_async("dif_csr_build", status, 8, st)) return rc;            // {bad index flag, longest row}
+    if (transpose) {
+        if (int rc = zero_async("dif_csr_build", degc, static_cast<size_t>(N + 1) * 4, st)) return rc;
+    }
 
-    const int64_t cap = 8 * dif::kCUs;
     if (E == 0) {           // no entries: every pointer is 0
-        he = hipMemsetAsync(kcnt, 0, static_cast<size_t>(p.n_keys + 1) * 4, st);
-        if (he != hipSuccess) return dif::fail(static_cast<int>(he), "dif_csr_build: memset: %s", hipGetErrorString(he));
+        if (int rc = zero_async("dif_csr_build", kcnt, static_cast<size_t>(p.n_keys + 1) * 4, st)) return rc;
         hipLaunchKernelGGL(csr_ptrs_kernel, dim3(static_cast<unsigned>((N + 256) / 256)), dim3(256), 0, st, kcnt, N, p.NB,
                            rowptr, n_blocks > 1 ? blkptr : nullptr, degc, dinv, status + 1);
         return dif::launch_status("csr_ptrs_kernel");
     }
-    {
-        int64_t g = (E + 255) / 256;
-        if (g > cap) g = cap;
-        hipLaunchKernelGGL(csr_count_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, edge_index, E, N, p.NB,
-                           p.block_rows, transpose, edge_weight != nullptr, keys_a, vals_a, degc, status);
-        if (int rc = dif::launch_status("csr_count_kernel")) return rc;
-    }
-
-    uint32_t *kin = keys_a, *kout = keys_b, *vin = vals_a, *vout = vals_b;
-    const unsigned sort_grid = static_cast<unsigned>((p.n_chunks + kSortWaves - 1) / kSortWaves);
-    for (int pass = 0; pass < p.passes; ++pass) {
-        const int shift = pass * kRadixBits;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, E, shift,
-                           p.n_chunks, p.rounds, table);
-        if (int rc = dif::launch_status("radix_hist_kernel")) return rc;
-        if (int rc = exclusive_scan(table, p.table_len, table, nullptr, bsum, st)) return rc;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, vin, E, shift,
-                           p.n_chunks, p.rounds, table, kout, vout);
-        if (int rc = dif::launch_status("radix_scatter_kernel")) return rc;
-        uint32_t* t = kin; kin = kout; kout = t;
-        t = vin; vin = vout; vout = t;
-    }
-    int64_t g = (E + 1 + 255) / 256;
-    if (g > cap) g = cap;
+    hipLaunchKernelGGL(csr_count_kernel, dim3(capped_grid(E)), dim3(256), 0, st, edge_index, E, N, p.NB, p.block_rows,
+                       transpose, edge_weight != nullptr, b.kin, b.vin, degc, status);
+    if (int rc = dif::launch_status("csr_count_kernel")) return rc;
+    if (int rc = radix_sort(p.sort, b, st)) return rc;
+    const unsigned g = capped_grid(E + 1);
     // key pointers kptr[0 .. N*NB] from the sorted keys, then rowptr / blkptr / dinv
-    hipLaunchKernelGGL(csr_bounds_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, kin, E, p.n_keys, kcnt);
+    hipLaunchKernelGGL(csr_bounds_kernel, dim3(g), dim3(256), 0, st, b.kin, E, p.n_keys, kcnt);
     if (int rc = dif::launch_status("csr_bounds_kernel")) return rc;
     hipLaunchKernelGGL(csr_ptrs_kernel, dim3(static_cast<unsigned>((N + 256) / 256)), dim3(256), 0, st, kcnt, N, p.NB,
                        rowptr, n_blocks > 1 ? blkptr : nullptr, degc, dinv, status + 1);
     if (int rc = dif::launch_status("csr_ptrs_kernel")) return rc;
-    hipLaunchKernelGGL(csr_fill_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, edge_index, E, N,
-                       static_cast<uint32_t>(p.NB), transpose, edge_weight, kin, vin, dinv, src, val);
+    hipLaunchKernelGGL(csr_fill_kernel, dim3(g), dim3(256), 0, st, edge_index, E, N, static_cast<uint32_t>(p.NB), transpose,
+                       edge_weight, b.kin, b.vin, dinv, src, val);
     return dif::launch_status("csr_fill_kernel");
 }
-
-namespace {
-struct OrderPlan { int64_t n_chunks, table_len; size_t off_keys_a, off_keys_b, off_vals_a, off_table, off_bsum, total; };
-OrderPlan make_order_plan(int64_t n) {
-    OrderPlan p;
-    const int64_t chunk = 64 * kSortRoundsMin;
-    p.n_chunks = (n + chunk - 1) / chunk;
-    if (p.n_chunks < 1) p.n_chunks = 1;
-    p.table_len = p.n_chunks * kRadix;
-    const size_t e = static_cast<size_t>(n > 0 ? n : 1);
-    size_t o = 0;
-    p.off_keys_a = o; o += align256(e * 4);
-    p.off_keys_b = o; o += align256(e * 4);
-    p.off_vals_a = o; o += align256(e * 4);
-    p.off_table = o;  o += align256(static_cast<size_t>(p.table_len) * 4);
-    p.off_bsum = o;   o += align256(static_cast<size_t>((p.table_len + kScanTile - 1) / kScanTile + 1) * 4);
-    p.total = o;
-    return p;
-}
-}  // namespace
 
 extern "C" size_t dif_row_order_workspace_bytes(int64_t n_rows) {
     if (n_rows <= 0) return 0;
@@ -853,51 +910,23 @@ extern "C" int dif_row_order(const int32_t* rowptr, int64_t row_begin, int64_t n
                 "dif_row_order: need 0 < n_rows < 2^31, row_begin >= 0");
     DIF_REQUIRE(rowptr && order && stats && workspace, DIF_E_BADARG, "dif_row_order: null pointer");
     const OrderPlan p = make_order_plan(n_rows);
-    DIF_REQUIRE(workspace_bytes >= p.total, DIF_E_WORKSPACE, "dif_row_order: workspace too small (%zu < %zu)",
-                workspace_bytes, p.total);
-    DIF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, DIF_E_BADARG,
-                "dif_row_order: workspace must be 256-byte aligned");
+    if (int rc = check_workspace("dif_row_order", workspace, workspace_bytes, p.total)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
-    uint32_t* kin = reinterpret_cast<uint32_t*>(ws + p.off_keys_a);
-    uint32_t* kout = reinterpret_cast<uint32_t*>(ws + p.off_keys_b);
-    uint32_t* vin = reinterpret_cast<uint32_t*>(ws + p.off_vals_a);
-    uint32_t* vout = reinterpret_cast<uint32_t*>(order);            // 3 passes: a -> order -> a -> order
-    int32_t* table = reinterpret_cast<int32_t*>(ws + p.off_table);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + p.off_bsum);
-    hipError_t he = hipMemsetAsync(stats, 0, 8, st);
-    if (he != hipSuccess) return dif::fail(static_cast<int>(he), "dif_row_order: memset: %s", hipGetErrorString(he));
+    // 3 passes: a -> order -> a -> order
+    static_assert(kOrderPasses % 2 == 1, "an odd number of passes is what leaves the sorted row ids in `order`");
+    SortBufs b{at<uint32_t>(ws, p.off_ka), at<uint32_t>(ws, p.off_kb), at<uint32_t>(ws, p.off_va), reinterpret_cast<uint32_t*>(order),
+               at<int32_t>(ws, p.off_table), at<int32_t>(ws, p.off_bsum)};
+    if (int rc = zero_async("dif_row_order", stats, 8, st)) return rc;
     hipLaunchKernelGGL(order_keys_kernel, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0, st, rowptr,
-                       row_begin, n_rows, kin, vin, stats);
+                       row_begin, n_rows, b.kin, b.vin, stats);
     if (int rc = dif::launch_status("order_keys_kernel")) return rc;
-    const unsigned sort_grid = static_cast<unsigned>((p.n_chunks + kSortWaves - 1) / kSortWaves);
-    for (int pass = 0; pass < 3; ++pass) {
-        const int shift = pass * kRadixBits;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, n_rows, shift, p.n_chunks,
-                           kSortRoundsMin, table);
-        if (int rc = dif::launch_status("radix_hist_kernel")) return rc;
-        if (int rc = exclusive_scan(table, p.table_len, table, nullptr, bsum, st)) return rc;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, vin, n_rows, shift,
-                           p.n_chunks, kSortRoundsMin, table, kout, vout);
-        if (int rc = dif::launch_status("radix_scatter_kernel")) return rc;
-        uint32_t* t = kin; kin = kout; kout = t;
-        t = vin; vin = vout; vout = t;
-    }
-    return 0;
-}
-
-// workspace: newid [N] | mask words [ceil(E / 64)] | chunk counts [E / 4,096 + 2] | the scan's block sums | member bitmap [N / 32]
-inline size_t sub_mask_bytes(int64_t E) { return align256(static_cast<size_t>((E + 63) / 64 + 1) * 8); }
-inline size_t sub_count_bytes(int64_t E) { return align256(static_cast<size_t>((E + kSubChunk - 1) / kSubChunk + 2) * 4); }
-inline size_t sub_bsum_bytes(int64_t E) {
-    const int64_t n = (E + kSubChunk - 1) / kSubChunk + 1;
-    return align256(static_cast<size_t>((n + kScanTile - 1) / kScanTile + 1) * 4);
+    return radix_sort(p.sort, b, st);
 }
 
 extern "C" size_t dif_subgraph_workspace_bytes(int64_t E, int64_t N) {
     if (E < 0 || N <= 0) return 0;
-    return align256(static_cast<size_t>(N) * 4) + sub_mask_bytes(E) + sub_count_bytes(E) + sub_bsum_bytes(E) +
-           align256(static_cast<size_t>((N + 31) / 32) * 4);
+    return make_sub_plan(E, N).total;
 }
 
 extern "C" int dif_subgraph(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* subset, int64_t B,
@@ -910,42 +939,29 @@ extern "C" int dif_subgraph(const int64_t* edge_index, int64_t E, int64_t N, con
                 DIF_E_BADARG, "dif_subgraph: null pointer");
     DIF_REQUIRE((edge_weight == nullptr) == (out_weight == nullptr), DIF_E_BADARG,
                 "dif_subgraph: edge_weight and out_weight must be given together");
-    DIF_REQUIRE(workspace_bytes >= dif_subgraph_workspace_bytes(E, N), DIF_E_WORKSPACE, "dif_subgraph: workspace too small");
-    DIF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, DIF_E_BADARG,
-                "dif_subgraph: workspace must be 256-byte aligned");
+    const SubPlan p = make_sub_plan(E, N);
+    if (int rc = check_workspace("dif_subgraph", workspace, workspace_bytes, p.total)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
-    int32_t* newid = reinterpret_cast<int32_t*>(ws);
-    char* at = ws + align256(static_cast<size_t>(N) * 4);
-    unsigned long long* mask = reinterpret_cast<unsigned long long*>(at);
-    at += sub_mask_bytes(E);
-    int32_t* counts = reinterpret_cast<int32_t*>(at);
-    at += sub_count_bytes(E);
-    int32_t* bsum = reinterpret_cast<int32_t*>(at);
-    at += sub_bsum_bytes(E);
-    uint32_t* member = reinterpret_cast<uint32_t*>(at);
-    hipError_t he = hipMemsetAsync(newid, 0, static_cast<size_t>(N) * 4, st);
-    if (he == hipSuccess) he = hipMemsetAsync(member, 0, static_cast<size_t>((N + 31) / 32) * 4, st);
-    if (he == hipSuccess) he = hipMemsetAsync(status, 0, 4, st);
-    if (he != hipSuccess) return dif::fail(static_cast<int>(he), "dif_subgraph: memset: %s", hipGetErrorString(he));
+    int32_t* newid = at<int32_t>(ws, p.off_newid);
+    unsigned long long* mask = at<unsigned long long>(ws, p.off_mask);
+    int32_t* counts = at<int32_t>(ws, p.off_counts);
+    int32_t* bsum = at<int32_t>(ws, p.off_bsum);
+    uint32_t* member = at<uint32_t>(ws, p.off_member);
+    if (int rc = zero_async("dif_subgraph", newid, static_cast<size_t>(N) * 4, st)) return rc;
+    if (int rc = zero_async("dif_subgraph", member, static_cast<size_t>((N + 31) / 32) * 4, st)) return rc;
+    if (int rc = zero_async("dif_subgraph", status, 4, st)) return rc;
     if (B > 0) {
         hipLaunchKernelGGL(subgraph_mark_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, st, subset, B,
                            N, newid, member, status);
         if (int rc = dif::launch_status("subgraph_mark_kernel")) return rc;
     }
-    const int64_t n_chunks = (E + kSubChunk - 1) / kSubChunk;
-    const int64_t cap = 8 * dif::kCUs;
-    int64_t g = n_chunks + 1;
-    if (g > cap) g = cap;
-    hipLaunchKernelGGL(subgraph_mask_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, edge_index, E, N, member, mask,
-                       counts, n_chunks, status);
+    hipLaunchKernelGGL(subgraph_mask_kernel, dim3(capped_blocks(p.n_chunks + 1)), dim3(256), 0, st, edge_index, E, N, member,
+                       mask, counts, p.n_chunks, status);
     if (int rc = dif::launch_status("subgraph_mask_kernel")) return rc;
-    if (int rc = exclusive_scan(counts, n_chunks + 1, counts, nullptr, bsum, st)) return rc;
-    int64_t g2 = (n_chunks + 3) / 4;
-    if (g2 > cap) g2 = cap;
-    if (g2 < 1) g2 = 1;
-    hipLaunchKernelGGL(subgraph_compact_kernel, dim3(static_cast<unsigned>(g2)), dim3(256), 0, st, edge_index, E, edge_weight,
-                       newid, mask, counts, n_chunks, E, out_edge_index, out_weight, out_count);
+    if (int rc = exclusive_scan(counts, p.n_chunks + 1, counts, nullptr, bsum, st)) return rc;
+    hipLaunchKernelGGL(subgraph_compact_kernel, dim3(capped_blocks((p.n_chunks + 3) / 4)), dim3(256), 0, st, edge_index, E,
+                       edge_weight, newid, mask, counts, p.n_chunks, E, out_edge_index, out_weight, out_count);
     return dif::launch_status("subgraph_compact_kernel");
 }
 
@@ -962,51 +978,27 @@ extern "C" int dif_subgraph_batches_group(const int64_t* edge_index, int64_t E, 
     DIF_REQUIRE(N > 0 && E >= 0 && M > 0 && batch_size > 0, DIF_E_BADARG, "dif_subgraph_batches: need N, M, batch_size > 0, E >= 0");
     DIF_REQUIRE(E < (int64_t(1) << 31) - 4096 && N < (int64_t(1) << 31) - 1 && M <= N && batch_size < (int64_t(1) << 31),
                 DIF_E_RANGE, "dif_subgraph_batches: sizes must fit int32 and M <= N");
-    const int64_t nb64 = (M + batch_size - 1) / batch_size;
-    DIF_REQUIRE(nb64 < 65535, DIF_E_RANGE, "dif_subgraph_batches: at most 65,534 batches");
-    const int n_batches = static_cast<int>(nb64);
+    int n_batches;
+    if (int rc = batch_count(M, batch_size, &n_batches)) return rc;
     DIF_REQUIRE(batch_ptr && status && workspace && perm && (E == 0 || edge_index), DIF_E_BADARG, "dif_subgraph_batches: null pointer");
     const BatchPlan p = make_batch_plan(E, N, n_batches);
-    DIF_REQUIRE(workspace_bytes >= p.total, DIF_E_WORKSPACE, "dif_subgraph_batches: workspace too small");
-    DIF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, DIF_E_BADARG, "dif_subgraph_batches: workspace must be 256-byte aligned");
+    if (int rc = check_workspace("dif_subgraph_batches", workspace, workspace_bytes, p.total)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
-    int32_t* info = reinterpret_cast<int32_t*>(ws + p.off_info);
-    uint32_t *ka = reinterpret_cast<uint32_t*>(ws + p.off_ka), *kb = reinterpret_cast<uint32_t*>(ws + p.off_kb);
-    uint32_t *va = reinterpret_cast<uint32_t*>(ws + p.off_va), *vb = reinterpret_cast<uint32_t*>(ws + p.off_vb);
-    int32_t* table = reinterpret_cast<int32_t*>(ws + p.off_table);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + p.off_bsum);
-    hipError_t he = hipMemsetAsync(info, 0, static_cast<size_t>(N) * 4, st);
-    if (he == hipSuccess) he = hipMemsetAsync(status, 0, 4, st);
-    if (he != hipSuccess) return dif::fail(static_cast<int>(he), "dif_subgraph_batches: memset: %s", hipGetErrorString(he));
+    int32_t* info = at<int32_t>(ws, p.off_info);
+    SortBufs b = sort_bufs(ws, p);
+    if (int rc = zero_async("dif_subgraph_batches", info, static_cast<size_t>(N) * 4, st)) return rc;
+    if (int rc = zero_async("dif_subgraph_batches", status, 4, st)) return rc;
     hipLaunchKernelGGL(batches_mark_kernel, dim3(static_cast<unsigned>((M + 255) / 256)), dim3(256), 0, st, perm, M, N, info, status);
     if (int rc = dif::launch_status("batches_mark_kernel")) return rc;
-    const int64_t cap = 8 * dif::kCUs;
-    int64_t g = (E + 1 + 255) / 256;
-    if (g > cap) g = cap;
-    if (E > 0) {
-        hipLaunchKernelGGL(batches_key_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, edge_index, E, N, info,
-                           static_cast<int32_t>(batch_size), p.passes > 1 ? 1 : 0, ka, va, status);
-        if (int rc = dif::launch_status("batches_key_kernel")) return rc;
-        const unsigned sort_grid = static_cast<unsigned>((p.n_chunks + kSortWaves - 1) / kSortWaves);
-        uint32_t *kin = ka, *kout = kb, *vin = va, *vout = vb;
-        for (int pass = 0; pass < p.passes; ++pass) {
-            const int shift = pass * kRadixBits;
-            hipLaunchKernelGGL(radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, E, shift, p.n_chunks, p.rounds, table);
-            if (int rc = dif::launch_status("radix_hist_kernel")) return rc;
-            if (int rc = exclusive_scan(table, p.table_len, table, nullptr, bsum, st)) return rc;
-            hipLaunchKernelGGL(radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, vin, E, shift, p.n_chunks,
-                               p.rounds, table, kout, vout);
-            if (int rc = dif::launch_status("radix_scatter_kernel")) return rc;
-            uint32_t* t = kin; kin = kout; kout = t;
-            t = vin; vin = vout; vout = t;
-        }
-        // sorted keys / ids now sit in (kin, vin): after one pass that is (kb, vb), after two (ka, va)
-        hipLaunchKernelGGL(batches_ptr_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, kin, E, n_batches, batch_ptr);
-        return dif::launch_status("batches_ptr_kernel");
-    }
-    he = hipMemsetAsync(batch_ptr, 0, static_cast<size_t>(n_batches + 1) * 8, st);
-    return he == hipSuccess ? 0 : dif::fail(static_cast<int>(he), "dif_subgraph_batches: memset: %s", hipGetErrorString(he));
+    if (E == 0) return zero_async("dif_subgraph_batches", batch_ptr, static_cast<size_t>(n_batches + 1) * 8, st);
+    const unsigned g = capped_grid(E + 1);
+    hipLaunchKernelGGL(batches_key_kernel, dim3(g), dim3(256), 0, st, edge_index, E, N, info, static_cast<int32_t>(batch_size),
+                       p.sort.passes > 1 ? 1 : 0, b.kin, b.vin, status);
+    if (int rc = dif::launch_status("batches_key_kernel")) return rc;
+    if (int rc = radix_sort(p.sort, b, st)) return rc;      // the ids end up at p.off_grouped()
+    hipLaunchKernelGGL(batches_ptr_kernel, dim3(g), dim3(256), 0, st, b.kin, E, n_batches, batch_ptr);
+    return dif::launch_status("batches_ptr_kernel");
 }
 
 // Phase 2: out_edge_index int64 [2, capacity] (row r at offset r * capacity), capacity >= batch_ptr[n_batches]:
@@ -1016,9 +1008,8 @@ extern "C" int dif_subgraph_batches_emit(const int64_t* edge_index, int64_t E, i
                                          int64_t* out_edge_index, float* out_weight, const void* workspace,
                                          size_t workspace_bytes, dif_stream_t stream) {
     DIF_REQUIRE(N > 0 && E >= 0 && M > 0 && batch_size > 0 && capacity >= 0, DIF_E_BADARG, "dif_subgraph_batches_emit: bad sizes");
-    const int64_t nb64 = (M + batch_size - 1) / batch_size;
-    DIF_REQUIRE(nb64 < 65535, DIF_E_RANGE, "dif_subgraph_batches: at most 65,534 batches");
-    const int n_batches = static_cast<int>(nb64);
+    int n_batches;
+    if (int rc = batch_count(M, batch_size, &n_batches)) return rc;
     DIF_REQUIRE(batch_ptr && workspace && (capacity == 0 || (edge_index && out_edge_index)), DIF_E_BADARG, "dif_subgraph_batches_emit: null pointer");
     DIF_REQUIRE((edge_weight == nullptr) == (out_weight == nullptr), DIF_E_BADARG,
                 "dif_subgraph_batches_emit: edge_weight and out_weight must be given together");
@@ -1026,13 +1017,9 @@ extern "C" int dif_subgraph_batches_emit(const int64_t* edge_index, int64_t E, i
     DIF_REQUIRE(workspace_bytes >= p.total, DIF_E_WORKSPACE, "dif_subgraph_batches_emit: workspace too small");
     if (capacity == 0 || E == 0) return 0;
     const char* ws = static_cast<const char*>(workspace);
-    const int32_t* info = reinterpret_cast<const int32_t*>(ws + p.off_info);
-    const uint32_t* vals = reinterpret_cast<const uint32_t*>(ws + (p.passes == 1 ? p.off_vb : p.off_va));
-    int64_t g = (capacity + 255) / 256;
-    if (g > 8 * dif::kCUs) g = 8 * dif::kCUs;
-    hipLaunchKernelGGL(batches_emit_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, static_cast<hipStream_t>(stream), edge_index,
-                       E, edge_weight, info, static_cast<int32_t>(batch_size), vals, batch_ptr, n_batches, capacity,
-                       out_edge_index, out_weight);
+    hipLaunchKernelGGL(batches_emit_kernel, dim3(capped_grid(capacity)), dim3(256), 0, static_cast<hipStream_t>(stream), edge_index,
+                       E, edge_weight, at<int32_t>(ws, p.off_info), static_cast<int32_t>(batch_size),
+                       at<uint32_t>(ws, p.off_grouped()), batch_ptr, n_batches, capacity, out_edge_index, out_weight);
     return dif::launch_status("batches_emit_kernel");
 }
 
@@ -1052,53 +1039,32 @@ extern "C" int dif_subgraph_batches_csr(const int64_t* edge_index, int64_t E, in
                                         size_t group_workspace_bytes, int32_t* rowptr, int32_t* src, float* val,
                                         void* workspace, size_t workspace_bytes, dif_stream_t stream) {
     DIF_REQUIRE(N > 0 && E >= 0 && M > 0 && batch_size > 0 && kept >= 0 && kept <= E, DIF_E_BADARG, "dif_subgraph_batches_csr: bad sizes");
-    const int64_t nb64 = (M + batch_size - 1) / batch_size;
-    DIF_REQUIRE(nb64 < 65535, DIF_E_RANGE, "dif_subgraph_batches: at most 65,534 batches");
+    int n_batches;
+    if (int rc = batch_count(M, batch_size, &n_batches)) return rc;
     DIF_REQUIRE(rowptr && group_workspace && workspace && (kept == 0 || (edge_index && src && val)), DIF_E_BADARG,
                 "dif_subgraph_batches_csr: null pointer");
-    const BatchPlan gp = make_batch_plan(E, N, static_cast<int>(nb64));
+    const BatchPlan gp = make_batch_plan(E, N, n_batches);
     DIF_REQUIRE(group_workspace_bytes >= gp.total, DIF_E_WORKSPACE, "dif_subgraph_batches_csr: group workspace too small");
     const BatchCsrPlan p = make_batch_csr_plan(kept, M);
-    DIF_REQUIRE(workspace_bytes >= p.total, DIF_E_WORKSPACE, "dif_subgraph_batches_csr: workspace too small");
-    DIF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, DIF_E_BADARG, "dif_subgraph_batches_csr: workspace must be 256-byte aligned");
+    if (int rc = check_workspace("dif_subgraph_batches_csr", workspace, workspace_bytes, p.total)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const char* gws = static_cast<const char*>(group_workspace);
-    const int32_t* info = reinterpret_cast<const int32_t*>(gws + gp.off_info);
-    const uint32_t* grouped = reinterpret_cast<const uint32_t*>(gws + (gp.passes == 1 ? gp.off_vb : gp.off_va));
+    const int32_t* info = at<int32_t>(gws, gp.off_info);
+    const uint32_t* grouped = at<uint32_t>(gws, gp.off_grouped());
     char* ws = static_cast<char*>(workspace);
-    uint32_t *ka = reinterpret_cast<uint32_t*>(ws + p.off_ka), *kb = reinterpret_cast<uint32_t*>(ws + p.off_kb);
-    uint32_t *va = reinterpret_cast<uint32_t*>(ws + p.off_va), *vb = reinterpret_cast<uint32_t*>(ws + p.off_vb);
-    float* dinv = reinterpret_cast<float*>(ws + p.off_dinv);
-    int32_t* table = reinterpret_cast<int32_t*>(ws + p.off_table);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + p.off_bsum);
-    if (kept == 0) {
-        hipError_t he = hipMemsetAsync(rowptr, 0, static_cast<size_t>(M + 1) * 4, st);
-        return he == hipSuccess ? 0 : dif::fail(static_cast<int>(he), "dif_subgraph_batches_csr: memset: %s", hipGetErrorString(he));
-    }
-    const int64_t cap = 8 * dif::kCUs;
-    int64_t g = (kept + 1 + 255) / 256;
-    if (g > cap) g = cap;
-    hipLaunchKernelGGL(batches_csr_key_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, edge_index, E, info, grouped, kept, ka, va);
+    SortBufs b = sort_bufs(ws, p);
+    float* dinv = at<float>(ws, p.off_dinv);
+    if (kept == 0) return zero_async("dif_subgraph_batches_csr", rowptr, static_cast<size_t>(M + 1) * 4, st);
+    const unsigned g = capped_grid(kept + 1);
+    hipLaunchKernelGGL(batches_csr_key_kernel, dim3(g), dim3(256), 0, st, edge_index, E, info, grouped, kept, b.kin, b.vin);
     if (int rc = dif::launch_status("batches_csr_key_kernel")) return rc;
-    const unsigned sort_grid = static_cast<unsigned>((p.n_chunks + kSortWaves - 1) / kSortWaves);
-    uint32_t *kin = ka, *kout = kb, *vin = va, *vout = vb;
-    for (int pass = 0; pass < p.passes; ++pass) {
-        const int shift = pass * kRadixBits;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, kept, shift, p.n_chunks, p.rounds, table);
-        if (int rc = dif::launch_status("radix_hist_kernel")) return rc;
-        if (int rc = exclusive_scan(table, p.table_len, table, nullptr, bsum, st)) return rc;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, vin, kept, shift, p.n_chunks,
-                           p.rounds, table, kout, vout);
-        if (int rc = dif::launch_status("radix_scatter_kernel")) return rc;
-        uint32_t* t = kin; kin = kout; kout = t;
-        t = vin; vin = vout; vout = t;
-    }
-    hipLaunchKernelGGL(csr_bounds_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, kin, kept, M, rowptr);
+    if (int rc = radix_sort(p.sort, b, st)) return rc;
+    hipLaunchKernelGGL(csr_bounds_kernel, dim3(g), dim3(256), 0, st, b.kin, kept, M, rowptr);
     if (int rc = dif::launch_status("csr_bounds_kernel")) return rc;
     hipLaunchKernelGGL(batches_csr_dinv_kernel, dim3(static_cast<unsigned>((M + 255) / 256)), dim3(256), 0, st, rowptr, M, dinv);
     if (int rc = dif::launch_status("batches_csr_dinv_kernel")) return rc;
-    hipLaunchKernelGGL(batches_csr_fill_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, edge_index, E, edge_weight, info,
-                       static_cast<int32_t>(batch_size), kin, vin, kept, dinv, src, val);
+    hipLaunchKernelGGL(batches_csr_fill_kernel, dim3(g), dim3(256), 0, st, edge_index, E, edge_weight, info,
+                       static_cast<int32_t>(batch_size), b.kin, b.vin, kept, dinv, src, val);
     return dif::launch_status("batches_csr_fill_kernel");
 }
 
@@ -1116,59 +1082,35 @@ extern "C" int dif_graph_prepare(const int64_t* edge_index, int64_t E, int64_t N
                                  int32_t* status, void* workspace, size_t workspace_bytes, dif_stream_t stream) {
     DIF_REQUIRE(N > 0 && E >= 0, DIF_E_BADARG, "dif_graph_prepare: need N > 0, E >= 0");
     const PrepPlan p = make_prep_plan(E, N, undirected);
-    DIF_REQUIRE(p.n < (int64_t(1) << 31) - 4096 && N < (int64_t(1) << 31) - 1, DIF_E_RANGE, "dif_graph_prepare: sizes must fit int32");
-    DIF_REQUIRE(capacity >= p.n + (add_loops ? N : 0), DIF_E_BADARG, "dif_graph_prepare: capacity too small");
+    const int64_t n = p.sort.n;                 // pairs: 2E when undirected
+    DIF_REQUIRE(n < (int64_t(1) << 31) - 4096 && N < (int64_t(1) << 31) - 1, DIF_E_RANGE, "dif_graph_prepare: sizes must fit int32");
+    DIF_REQUIRE(capacity >= n + (add_loops ? N : 0), DIF_E_BADARG, "dif_graph_prepare: capacity too small");
     DIF_REQUIRE(out_edge_index && out_count && status && workspace && (E == 0 || edge_index), DIF_E_BADARG, "dif_graph_prepare: null pointer");
-    DIF_REQUIRE(workspace_bytes >= p.total, DIF_E_WORKSPACE, "dif_graph_prepare: workspace too small");
-    DIF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, DIF_E_BADARG, "dif_graph_prepare: workspace must be 256-byte aligned");
+    if (int rc = check_workspace("dif_graph_prepare", workspace, workspace_bytes, p.total)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
-    uint32_t *ka = reinterpret_cast<uint32_t*>(ws + p.off_ka), *kb = reinterpret_cast<uint32_t*>(ws + p.off_kb);
-    uint32_t *va = reinterpret_cast<uint32_t*>(ws + p.off_va), *vb = reinterpret_cast<uint32_t*>(ws + p.off_vb);
-    int32_t* keep = reinterpret_cast<int32_t*>(ws + p.off_keep);
-    int32_t* table = reinterpret_cast<int32_t*>(ws + p.off_table);
-    int32_t* bsum = reinterpret_cast<int32_t*>(ws + p.off_bsum);
-    hipError_t he = hipMemsetAsync(status, 0, 4, st);
-    if (he != hipSuccess) return dif::fail(static_cast<int>(he), "dif_graph_prepare: memset: %s", hipGetErrorString(he));
-    const int64_t cap = 8 * dif::kCUs;
-    int64_t g = (p.n + 1 + 255) / 256;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    uint32_t *row = va, *col = ka;           // after prep_pairs: key = col, payload = row
+    SortBufs b = sort_bufs(ws, p);
+    int32_t* keep = at<int32_t>(ws, p.off_keep);
+    if (int rc = zero_async("dif_graph_prepare", status, 4, st)) return rc;
+    const unsigned g = capped_grid(n + 1);
+    uint32_t *row = b.vin, *col = b.kin;           // after prep_pairs: key = col, payload = row
     if (E > 0) {
-        hipLaunchKernelGGL(prep_pairs_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, edge_index, E, N, undirected, ka, va, status);
+        hipLaunchKernelGGL(prep_pairs_kernel, dim3(g), dim3(256), 0, st, edge_index, E, N, undirected, b.kin, b.vin, status);
         if (int rc = dif::launch_status("prep_pairs_kernel")) return rc;
     }
-    if (undirected && p.n > 0) {
-        const unsigned sort_grid = static_cast<unsigned>((p.n_chunks + kSortWaves - 1) / kSortWaves);
-        uint32_t *kin = ka, *kout = kb, *vin = va, *vout = vb;
-        for (int phase = 0; phase < 2; ++phase) {          // phase 0: by col, phase 1: by row (stable) -> (row, col) order
-            for (int pass = 0; pass < p.passes; ++pass) {
-                const int shift = pass * kRadixBits;
-                hipLaunchKernelGGL(radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, p.n, shift, p.n_chunks, p.rounds, table);
-                if (int rc = dif::launch_status("radix_hist_kernel")) return rc;
-                if (int rc = exclusive_scan(table, p.table_len, table, nullptr, bsum, st)) return rc;
-                hipLaunchKernelGGL(radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, kin, vin, p.n, shift, p.n_chunks,
-                                   p.rounds, table, kout, vout);
-                if (int rc = dif::launch_status("radix_scatter_kernel")) return rc;
-                uint32_t* t = kin; kin = kout; kout = t;
-                t = vin; vin = vout; vout = t;
-            }
-            if (phase == 0) {                               // keys <- rows, payload <- cols
-                hipLaunchKernelGGL(prep_swap_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, kin, vin, p.n);
-                if (int rc = dif::launch_status("prep_swap_kernel")) return rc;
-            }
-        }
-        row = kin;
-        col = vin;
+    if (undirected && n > 0) {
+        // by col, then (stable) by row -> (row, col) order; in between keys <- rows, payload <- cols
+        if (int rc = radix_sort(p.sort, b, st)) return rc;
+        hipLaunchKernelGGL(prep_swap_kernel, dim3(g), dim3(256), 0, st, b.kin, b.vin, n);
+        if (int rc = dif::launch_status("prep_swap_kernel")) return rc;
+        if (int rc = radix_sort(p.sort, b, st)) return rc;
+        row = b.kin;
+        col = b.vin;
     }
-    hipLaunchKernelGGL(prep_flag_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, row, col, p.n, undirected, remove_loops, keep);
+    hipLaunchKernelGGL(prep_flag_kernel, dim3(g), dim3(256), 0, st, row, col, n, undirected, remove_loops, keep);
     if (int rc = dif::launch_status("prep_flag_kernel")) return rc;
-    if (int rc = exclusive_scan(keep, p.n + 1, keep, nullptr, bsum, st)) return rc;
-    int64_t g2 = ((p.n > N ? p.n : N) + 255) / 256;
-    if (g2 > cap) g2 = cap;
-    if (g2 < 1) g2 = 1;
-    hipLaunchKernelGGL(prep_emit_kernel, dim3(static_cast<unsigned>(g2)), dim3(256), 0, st, row, col, p.n, keep, N, add_loops, capacity,
-                       out_edge_index, out_count);
+    if (int rc = exclusive_scan(keep, n + 1, keep, nullptr, b.bsum, st)) return rc;
+    hipLaunchKernelGGL(prep_emit_kernel, dim3(capped_grid(n > N ? n : N)), dim3(256), 0, st, row, col, n, keep, N, add_loops,
+                       capacity, out_edge_index, out_count);
     return dif::launch_status("prep_emit_kernel");
 }

@@ -151,6 +151,26 @@ def test_abi_3_version_and_size_helpers(lib):
     assert lib.dif_sigmoid_workspace_bytes(2708, 2708, 1, 64, 64) > 0            # Cora: keys split over workgroups
 
 
+GRAPH_WORKSPACE_BYTES = {
+    "dif_csr_workspace_bytes": {(0, 1, 1): 3072, (1, 1, 1): 3072, (1000, 100, 1): 20224, (511, 4096, 3): 92160,          # (E, N, n_blocks)
+                                (262145, 70000, 13): 8924416, (79255038, 132534, 13): 1295866624},
+    "dif_row_order_workspace_bytes": {(1,): 2048, (512,): 7424, (513,): 9216, (132534,): 1856256},                       # (n_rows)
+    "dif_subgraph_workspace_bytes": {(0, 5): 1280, (4096, 33): 1792, (4097, 1000): 5632},                                # (E, N)
+    "dif_subgraph_batches_workspace_bytes": {(0, 10, 1): 2560, (1000, 100, 254): 19200, (1000, 100, 255): 19200,         # (E, N, n_batches)
+                                             (300000, 70000, 7): 5681408},
+    "dif_subgraph_batches_csr_workspace_bytes": {(0, 5): 2560, (1000, 100): 19200, (300000, 65537): 5663744},            # (kept, M)
+    "dif_graph_prepare_workspace_bytes": {(0, 5, 0): 2560, (1000, 100, 1): 45312, (1000, 100, 0): 22784,                 # (E, N, undirected)
+                                          (300000, 70000, 1): 13202944},
+}
+
+
+def test_graph_construction_workspace_sizes_are_pinned(lib):
+    """The workspace layouts of csrc/gcn_csr.hip: the Python side sizes its allocations from these helpers and the batches
+    workspace is read back by two later calls, so the totals are part of the contract (host arithmetic, no device)."""
+    got = {name: {args: getattr(lib, name)(*args) for args in cases} for name, cases in GRAPH_WORKSPACE_BYTES.items()}
+    assert got == GRAPH_WORKSPACE_BYTES
+
+
 def test_sliced_plan_is_host_side_arithmetic(lib):
     """dif_sliced_plan: geometry of the feature-sliced product (no device call)."""
     plan = (ctypes.c_int32 * 8)()

@@ -62,6 +62,17 @@ def test_every_shared_helper_is_defined_exactly_once():
     assert counts == {name: 1 for name in SHARED}, counts
 
 
+def test_the_radix_pass_kernels_are_launched_from_one_place():
+    """csrc/gcn_csr.hip: every sort of the graph construction goes through the one pass loop."""
+    text = sources()["gcn_csr.hip"]
+    assert text.count("hipLaunchKernelGGL(radix_hist_kernel") == 1
+    assert text.count("hipLaunchKernelGGL(radix_scatter_kernel") == 1
+
+
+def test_the_sort_rounds_formula_is_written_once():
+    assert sources()["gcn_csr.hip"].count("64 * 4096") == 1
+
+
 def test_the_definition_finder_sees_a_copy():
     copy = "namespace {\ntemplate <bool VEC>\n__device__ __forceinline__ f32x4 ld4(const float* __restrict__ base, int64_t ld,\n   int width) {\n    return f32x4{};\n}\n}"
     assert len(definitions(copy, "ld4")) == 1 and not definitions(copy, "ld4_raw")

@@ -340,7 +340,7 @@ def test_gcn_conv_golden(name, dev):
 @pytest.mark.parametrize("n,e,h,d,weighted", [(2708, 13264, 1, 64, False), (5000, 400000, 1, 64, True),
                                               (3000, 50000, 2, 32, False), (1000, 20000, 1, 300, True),
                                               (4000, 30000, 1, 10, False), (100000, 330000, 1, 64, False),
-                                              (20000, 3000000, 1, 64, False)])
+                                              (20000, 3000000, 1, 64, False), (200, 3000, 1, 8, False)])
 def test_gcn_conv_vs_oracle(n, e, h, d, weighted, dev):
     from difformer_amd import gcn_conv, ops
     g = torch.Generator().manual_seed(e + n)
@@ -1161,7 +1161,9 @@ def test_subgraph_edge_counts_around_the_mask_words_and_chunks(n, e, bsz, dev):
 
 
 @pytest.mark.parametrize("n,e,m,bsz,weighted", [(50000, 1200000, 50000, 10000, True), (50000, 1200000, 31234, 7000, False),
-                                                 (3000, 40000, 3000, 10, False), (1000, 5000, 1000, 1000, True)])
+                                                 (3000, 40000, 3000, 10, False), (1000, 5000, 1000, 1000, True),
+                                                 (600, 3000, 508, 2, False), (600, 3000, 510, 2, True),
+                                                 (300, 2000, 200, 64, False), (70000, 5000, 66000, 33000, True)])
 def test_subgraph_batches_equal_the_per_batch_calls(n, e, m, bsz, weighted, dev):
     """All mini-batch subgraphs of an epoch from ONE pass over the edge list (main-batch.py:121-131): every batch must be
     exactly what subgraph(idx_i, edge_index, relabel_nodes=True) returns for it -- integer work, compared exactly
@@ -1448,7 +1450,7 @@ def _zipf_graph(n, e, seed, dev):
 
 
 @pytest.mark.parametrize("n,e,lo,cnt", [(5000, 200000, 0, 5000), (5000, 200000, 1234, 2001), (70000, 3000000, 0, 70000),
-                                        (70000, 3000000, 61250, 8750)])
+                                        (70000, 3000000, 61250, 8750), (700, 9000, 13, 513), (700, 9000, 100, 300)])
 def test_row_order_is_the_stable_degree_sort(n, e, lo, cnt, dev):
     """dif_row_order: bit-exact against a stable argsort of the shard's degrees (descending, ties by row)."""
     from difformer_amd import ops
