@@ -669,16 +669,19 @@ class HipBackend:
                    plan, _ptr(ys), _ptr(record), _ptr(ws), ws_bytes)
         return record, ys
 
-    def input_gram(self, x, weight, bias, ln_weight, ln_bias, eps, relu, rowptr=None, plan=None):
+    def input_gram(self, x, weight, bias, ln_weight, ln_bias, eps, relu, rowptr=None, plan=None, rows=True):
         """Input layer + the first closed-form layer's products in one pass (csrc/simple_layer.hip, input_gram_kernel):
-        x [n, C_in <= 64] fp32 -> (h = ReLU(LayerNorm(x W^T + b)) [n, D], record of h as `gram` leaves it, ys | None)."""
+        x [n, C_in <= 64] fp32 -> (h = ReLU(LayerNorm(x W^T + b)) [n, D], record of h as `gram` leaves it, ys | None).
+        rows=False (single copy; needs plan): h is not stored, the hidden rows exist as ys alone -> (None, record, ys)."""
         dev = _require_device(x, weight, bias, ln_weight, ln_bias, rowptr)
         _all_f32(x=x, weight=weight, bias=bias)
         n, C = x.shape
         D = weight.shape[0]
         x, ldx = _row_major(x, C)
         weight, bias, ln_weight, ln_bias = _contig(weight, bias, ln_weight, ln_bias)
-        out = torch.empty((n, D), dtype=torch.float32, device=dev)
+        if not rows and plan is None:
+            raise TypeError("difformer_amd: input_gram(rows=False) leaves the rows as the slice-major copy: it needs rowptr and plan")
+        out = torch.empty((n, D), dtype=torch.float32, device=dev) if rows else None
         record = torch.empty(D * D + D + 2, dtype=torch.float32, device=dev)
         ws_bytes = self.lib.dif_gram_workspace_bytes(n, D)
         ws = _workspace(ws_bytes, dev, floor=16)
@@ -780,15 +783,27 @@ class HipBackend:
 
     def simple_layer(self, x, coef, D, ax=None, Wv=None, bv=None, row_sums=None, gcn_scale=1.0, x0=None, residual=False,
                      alpha=0.5, ln_weight=None, ln_bias=None, eps=1e-5, relu=False, next_rowptr=None, next_plan=None,
-                     head=None, gather=None):
+                     head=None, gather=None, rscale=None, rows=True):
         """-> out [n, D]; with next_plan -> (out, ys): also the slice-major scaled copy of `out` for the next layer's SpMM
         (see gram()).
         head = (Wo [Co, D], bo [Co]) float32, Co <= 128 (the model's output Linear, difformer.py:208): -> logits [n, Co]
         from the same pass; the layer's rows themselves are not stored.
         gather = (rowptr, src, val) of a one-block CSR over the same n nodes: the aggregation runs inside the layer kernel
-        (no `ax`, no `row_sums`, no next-layer products)."""
-        dev = _require_device(x, coef, ax, Wv, bv, row_sums, x0, ln_weight, ln_bias)
-        n, C = x.shape
+        (no `ax`, no `row_sums`, no next-layer products).
+        rscale [n] float32 = deg^1/2 (single copy): x is not the rows [n, C] but their slice-major pre-scaled copy
+        [C/4, rows per slice, 4] (`ys` of gram / input_gram / a previous layer).  rows=False (with next_plan): `out` is not
+        stored either -> (None, ys)."""
+        dev = _require_device(x, coef, ax, Wv, bv, row_sums, x0, ln_weight, ln_bias, rscale)
+        if rscale is not None:
+            if (gather is not None or x.dim() != 3 or x.shape[2] != 4 or x.dtype != torch.float32 or not x.is_contiguous() or
+                    rscale.dtype != torch.float32 or not rscale.is_contiguous() or x.shape[1] < rscale.numel()):
+                raise TypeError("difformer_amd: rscale goes with the contiguous float32 slice-major copy [C/4, rows, 4] of the "
+                                "layer input and no in-kernel aggregation")
+            n, C = rscale.numel(), 4 * x.shape[0]
+        else:
+            n, C = x.shape
+        if not rows and (rscale is None or next_plan is None):
+            raise TypeError("difformer_amd: simple_layer(rows=False) is the single-copy mode: it needs rscale and next_plan")
         if gather is not None:
             rowptr, src, val = gather
             if (ax is not None or next_plan is not None or rowptr.numel() != n + 1 or rowptr.dtype != torch.int32 or
@@ -799,7 +814,10 @@ class HipBackend:
             row_sums = None
         dt, sfx = _storage(x, ax, x0)              # activations: float32 or bfloat16; parameters always float32 here
         _all_f32(coef=coef, Wv=Wv, bv=bv, ln_weight=ln_weight, ln_bias=ln_bias, row_sums=row_sums)
-        x, ldx = _rows(x, C, align=True)
+        if rscale is not None:
+            ldx = x.shape[1]                           # rows per slice
+        else:
+            x, ldx = _rows(x, C, align=True)
         ax, ldax = _rows(ax, C)
         x0, ldx0 = _rows(x0, D)
         Wv, bv, ln_weight, ln_bias = _contig(Wv, bv, ln_weight, ln_bias)
@@ -822,9 +840,9 @@ class HipBackend:
         if head is not None:
             logits = torch.empty((n, Co), dtype=dt, device=dev)
             self._call("dif_simple_layer_f32", "dif_simple_layer_head_" + sfx, dev, *args, None, 0, _ptr(Wo), _ptr(bo), Co,
-                       _ptr(logits), Co)
+                       _ptr(logits), Co, *((_ptr(rscale),) if sfx == "f32" else ()))
             return logits
-        out = torch.empty((n, D), dtype=dt, device=dev)
+        out = torch.empty((n, D), dtype=dt, device=dev) if rows else None
         if sfx == "bf16":
             if next_plan is not None:
                 raise TypeError("difformer_amd: products for the next layer are float32-only")
@@ -832,7 +850,8 @@ class HipBackend:
             return out
         ys = None if next_plan is None else _slice_major(D, next_plan, dev)
         self._call("dif_simple_layer_f32", "dif_simple_layer_f32", dev, *args, _ptr(out), D,
-                   _ptr(next_rowptr) if ys is not None else None, next_plan if ys is not None else None, _ptr(ys))
+                   _ptr(next_rowptr) if ys is not None else None, next_plan if ys is not None else None, _ptr(ys),
+                   _ptr(rscale))
         return out if next_plan is None else (out, ys)
 
     def _simple_layer_gather(self, dev, dt, sfx, n, D, args, Wo, bo, Co):
@@ -1013,25 +1032,32 @@ class HipBackend:
                    _ptr(d_conv), H * D, _ptr(d_x0), D, _ptr(d_prev), D, _ptr(d_ln), _ptr(ws), ws_bytes)
         return (d_conv, d_x0, d_prev, None if d_ln is None else d_ln[:D], None if d_ln is None else d_ln[D:2 * D])
 
-    def coeffs_bg(self, x, record, n_global, factors, C, D, attn_scale):
+    def coeffs_bg(self, x, record, n_global, factors, C, D, attn_scale, rscale=None):
         """Coefficients of the closed-form layer through the background kernels (csrc/side_chain.hip), enqueued on the
         CURRENT stream (the caller puts a side stream there): from x [n, C] (one pass: Gram partials per wave), or from a
         finished `record` [X^T X | sum x] when the layer input's Gram pass has already run.  factors:
-        ops.NarrowFactors (pt, vtt, st float32 [80 * 80]).  -> coef (layout of simple_coeffs)."""
-        dev = _require_device(x, record, factors.pt)
+        ops.NarrowFactors (pt, vtt, st float32 [80 * 80]).  -> coef (layout of simple_coeffs).
+        rscale [n] (single copy): x is the slice-major pre-scaled copy [C/4, rows per slice, 4] of the rows, as for simple_layer."""
+        dev = _require_device(x, record, factors.pt, rscale)
         f32 = dict(dtype=torch.float32, device=dev)
         gt = torch.empty(80 * 80 + 400, **f32)           # G~ + 100 float64 pairs of partial norm products
         if record is not None:
             ws, ws_bytes, xp, ldx, n = record, record.numel() * 4, None, 0, 1
         else:
             _f32(x, "x")
-            n = x.shape[0]
-            x, ldx = _row_major(x, C)
+            if rscale is not None:
+                if x.dim() != 3 or x.shape != (C // 4, x.shape[1], 4) or not x.is_contiguous() or x.shape[1] < rscale.numel():
+                    raise TypeError("difformer_amd: rscale goes with the contiguous slice-major copy [C/4, rows, 4]")
+                n, ldx = rscale.numel(), x.shape[1]
+                rscale = _f32(rscale, "rscale").contiguous()
+            else:
+                n = x.shape[0]
+                x, ldx = _row_major(x, C)
             ws_bytes = self.lib.dif_gram_bg_workspace_bytes(n, C)
             ws = _workspace(ws_bytes, dev, floor=16)
             xp = x
         self._call("dif_gram_bg_f32", "dif_gram_bg_f32", dev, _ptr(xp), ldx, n, C, int(n_global), _ptr(factors.st), _ptr(gt),
-                   _ptr(ws), ws_bytes)
+                   _ptr(ws), ws_bytes, _ptr(rscale) if xp is not None else None)
         scratch = torch.empty(80 * 80 + 4, **f32)
         coef = torch.empty(self.lib.dif_simple_coeffs_len(C, D), **f32)
         self._call("dif_simple_coeffs_bg_f32", "dif_simple_coeffs_bg_f32", dev, _ptr(gt), _ptr(factors.pt), _ptr(factors.vtt),

@@ -11,7 +11,8 @@
 // so the layer needs two small GEMMs and two dot products; the weight-only factors P~, V~^T, S~ are cached by the host.
 // All matrices are zero-padded to 80 x 80 floats (kB), the augmented index is 64, every operand is k-contiguous so a
 // lane's MFMA inputs are 16-byte loads:  D = M1 M2  with  A = M1[i][k],  B = M2^T[j][k].
-//   gram_bg_kernel      per wave: rows -> partial [G | sx] record (as gram_kernel, no fold across waves)
+//   gram_bg_kernel      per wave: rows -> partial [G | sx] record (as gram_kernel, no fold across waves); <true>: the rows come
+//                       from their slice-major pre-scaled copy (single copy, simple_layer.hip)
 //   finalize_bg_kernel  sums the partials into the padded G~ (fixed order: deterministic)
 //   coeffs_bg_kernel<0> 25 tile workgroups: T^T = (G~ V~)^T;  one more: |Q|^2, |K|^2, s
 //   coeffs_bg_kernel<1> 25 tile workgroups: R = P~ T -> coef = [MnT | cn | u | cd | s | |Q|^2 | |K|^2] (dif_simple_coeffs_f32's layout)
@@ -27,8 +28,11 @@ constexpr int kAug = 64;               // index of the augmented row / column
 constexpr int kBgChunksMax = 512;
 
 // ---- Gram partials: one wave = one workgroup = one partial record [G: C x C][sx: C] ------------------------
+// SC (single copy): x is the slice-major pre-scaled copy ys = dinv x (ldx = rows per slice) and the row is
+// ys[slice l15][row] * rscale[row]: the same lane -> (row, columns) map, so the partial record is built in the same order.
+template <bool SC>
 __global__ __launch_bounds__(64) void gram_bg_kernel(const float* __restrict__ x, int64_t ldx, int64_t n_rows, int C,
-                                                     float* __restrict__ ws, int64_t ws_stride) {
+                                                     float* __restrict__ ws, int64_t ws_stride, const float* __restrict__ rscale) {
     const int lane = threadIdx.x;
     const int l15 = lane & 15, lg = lane >> 4;
     const bool col_ok = 4 * l15 < C;
@@ -41,7 +45,10 @@ __global__ __launch_bounds__(64) void gram_bg_kernel(const float* __restrict__ x
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int64_t row = tile * 16 + 4 * u + lg;
-            xv[u] = (row < n_rows && col_ok) ? *reinterpret_cast<const f32x4*>(x + row * ldx + 4 * l15) : zero4();
+            if constexpr (SC)
+                xv[u] = (row < n_rows && col_ok) ? reinterpret_cast<const f32x4*>(x)[l15 * ldx + row] * rscale[row] : zero4();
+            else
+                xv[u] = (row < n_rows && col_ok) ? *reinterpret_cast<const f32x4*>(x + row * ldx + 4 * l15) : zero4();
         }
     };
     f32x4 nxt[4];
@@ -212,19 +219,23 @@ extern "C" size_t dif_gram_bg_workspace_bytes(int64_t n_rows, int C) {
 // gt float[80 * 80 + 400]: the zero-padded G~ = [[X^T X, sum x], [sum x^T, n_global]] (augmented index 64), followed by the 100
 // float64 pairs of partial norm products <S~q, G~>, <S~k, G~> (sfac = st of dif_simple_coeffs_bg_f32).  x == NULL: `workspace`
 // already holds ONE record [G | sx] (e.g. dif_gram_f32's, whose pass also wrote the slice-major copy) and is only re-laid.
+// rscale != NULL (single copy): x is the slice-major copy deg^-1/2 x of the rows, ldx its rows per slice, rscale = deg^1/2.
 extern "C" int dif_gram_bg_f32(const float* x, int64_t ldx, int64_t n_rows, int C, int64_t n_global, const float* sfac, float* gt,
-                               void* workspace, size_t workspace_bytes, dif_stream_t stream) {
+                               void* workspace, size_t workspace_bytes, const float* rscale, dif_stream_t stream) {
     DIF_REQUIRE(gt && sfac && workspace && n_rows > 0 && n_global > 0, DIF_E_BADARG, "dif_gram_bg: null pointer or no rows");
+    DIF_REQUIRE(!rscale || x, DIF_E_BADARG, "dif_gram_bg: rscale without the slice-major copy");
     DIF_REQUIRE(dif::aligned16(gt), DIF_E_BADARG, "dif_gram_bg: gt must be 16-byte aligned");
     DIF_REQUIRE(C > 0 && C <= 64 && C % 4 == 0, DIF_E_SHAPE, "dif_gram_bg: covers C <= 64, C %% 4 == 0 (got %d)", C);
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* ws = static_cast<float*>(workspace);
     int P = 1;
     if (x) {
-        DIF_REQUIRE(ldx >= C && ldx % 4 == 0 && dif::aligned16(x), DIF_E_BADARG, "dif_gram_bg: rows of x must be 16-byte aligned");
+        DIF_REQUIRE((rscale ? ldx >= n_rows : (ldx >= C && ldx % 4 == 0)) && dif::aligned16(x), DIF_E_BADARG,
+                    "dif_gram_bg: rows of x must be 16-byte aligned (slice-major copy: ldx = rows per slice >= n_rows)");
         DIF_REQUIRE(workspace_bytes >= dif_gram_bg_workspace_bytes(n_rows, C), DIF_E_WORKSPACE, "dif_gram_bg: workspace too small");
         P = bg_chunks(n_rows);
-        hipLaunchKernelGGL(gram_bg_kernel, dim3(P), dim3(64), 0, st, x, ldx, n_rows, C, ws, rec_stride(C));
+        if (rscale) hipLaunchKernelGGL(gram_bg_kernel<true>, dim3(P), dim3(64), 0, st, x, ldx, n_rows, C, ws, rec_stride(C), rscale);
+        else hipLaunchKernelGGL(gram_bg_kernel<false>, dim3(P), dim3(64), 0, st, x, ldx, n_rows, C, ws, rec_stride(C), rscale);
         if (int rc = dif::launch_status("gram_bg_kernel")) return rc;
     } else {
         DIF_REQUIRE(workspace_bytes >= static_cast<size_t>(C * C + C) * sizeof(float), DIF_E_WORKSPACE, "dif_gram_bg: record too small");

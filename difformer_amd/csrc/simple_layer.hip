@@ -214,7 +214,9 @@ __global__ __launch_bounds__(64 * kGramWaves, 2) void gram_kernel(const T* __res
 // A[i = l15][k = lg] / B[k = lg][j = l15], the operands of the row-contracting Gram MFMAs without a trip through LDS:
 //   acc[(ta, tb)] += sum over reg of mfma(y[ta][reg], y[tb][reg])  ->  G[4 (4 lg + reg) + ta][4 l15 + tb], as gram_kernel.
 // ------------------------------------------------------------------------------------------------------------
-template <int KQ>
+// ROWS = false (single copy): h is not stored row-major at all -- the slice-major copy is then the only copy of the hidden rows
+// (the closed-form layer kernels read it back through load_slices).
+template <int KQ, bool ROWS>
 __global__ __launch_bounds__(64 * kGramWaves, 2) void input_gram_kernel(const float* __restrict__ x, int64_t ldx, int64_t n_rows, int C_in,
                                                                         const float* __restrict__ W, const float* __restrict__ bias,
                                                                         int D, const float* __restrict__ ln_w,
@@ -315,7 +317,7 @@ __global__ __launch_bounds__(64 * kGramWaves, 2) void input_gram_kernel(const fl
             }
             if (!ok) h = zero4();                       // rows past the matrix / padding columns stay out of the record
             if (ok) {
-                *reinterpret_cast<f32x4*>(out + row * ldo + 4 * l15) = h;
+                if (ROWS) *reinterpret_cast<f32x4*>(out + row * ldo + 4 * l15) = h;
                 if (ys) ys[static_cast<int64_t>(l15) * npad + row] = h * dinv_of(rowptr, row);
             }
 #pragma unroll
@@ -680,6 +682,9 @@ struct LayerArgsT {
     const float* Wo; const float* bo; int Co; T* logits; int64_t ldl;
     // GATHER: the aggregation itself in this pass (sparse graphs: a few entries per row) -- CSR over destination rows
     const int32_t* g_rowptr; const int32_t* g_src; const float* g_val;
+    // SC (single copy): x is the slice-major pre-scaled copy ys = dinv x of the layer input (ldx = rows per slice) and
+    // rscale[r] = sqrt(deg_r) recovers the row, x[r] = ys[r] * rscale[r]
+    const float* rscale;
 };
 using LayerArgs = LayerArgsT<float>;
 
@@ -696,6 +701,21 @@ __device__ __forceinline__ void load_rows(f32x4 (&xa)[4], const T* __restrict__ 
             const int c = 16 * cq + 4 * lg;
             xa[cq] = (r < n && c < C) ? Elem<T>::ld4g(x + r * ldx + c) : zero4();
         }
+    }
+}
+
+// SC: the same fragment from the slice-major pre-scaled copy (ys[slice][row] = dinv[row] * x[row][4 slice .. + 3], npad rows per
+// slice): lane (lg, l15) takes slices 4 cq + lg of row r0 + l15 -- per load instruction four runs of 256 contiguous bytes, the
+// pattern the kernel WRITES the copy in -- and multiplies by rscale[row] = sqrt(deg).  Rows past n_rows are never touched.
+template <bool GUARD>
+__device__ __forceinline__ void load_slices(f32x4 (&xa)[4], const f32x4* __restrict__ xs, int64_t npad,
+                                            const float* __restrict__ rscale, int64_t r, int64_t n, int lg, int C) {
+    const bool row_ok = !GUARD || r < n;
+    const float rs = row_ok ? rscale[r] : 0.f;
+#pragma unroll
+    for (int cq = 0; cq < 4; ++cq) {
+        const int sl = 4 * cq + lg;
+        xa[cq] = (row_ok && (!GUARD || 4 * sl < C)) ? *dif::as_global(xs + static_cast<int64_t>(sl) * npad + r) * rs : zero4();
     }
 }
 
@@ -822,11 +842,16 @@ __device__ __forceinline__ void project_split(f32x4 (&y)[4], const f32x4 (&xa)[4
 #ifndef DIF_GATHER_WG
 #define DIF_GATHER_WG 4           // workgroups per CU the GATHER variants are compiled for
 #endif
-template <bool EXACT, bool GRAPH_W, typename T = float, bool HEAD = false, bool GATHER = false, bool SPLIT = false>
+// SC (single copy): every layer's rows exist ONCE in HBM, as the slice-major pre-scaled copy the sliced product reads.  The
+// kernel then reads its input from that copy (a.x, a.rscale: load_slices) and, between two layers, is launched without a
+// row-major output (a.out null): per layer 34 MB less read and 34 MB less written at 132,534 x 64.  Dense unweighted float32
+// graphs in which every node has an incoming entry (deg > 0: the row is recoverable).  Everything after the load is the same code.
+template <bool EXACT, bool GRAPH_W, typename T = float, bool HEAD = false, bool GATHER = false, bool SPLIT = false, bool SC = false>
 __global__ __launch_bounds__(64 * (HEAD ? kHeadWaves : kWaves),
                              HEAD ? (2 * kHeadWaves + 3) / 4 : (GATHER ? DIF_GATHER_WG : 4))
 void simple_layer_kernel(LayerArgsT<T> a) {
     static_assert(!SPLIT || EXACT, "split-bf16 products: the dense 64 x 64 float32 layers");
+    static_assert(!SC || (std::is_same<T, float>::value && !GATHER), "the slice-major copy is float32; it is no gather operand");
     constexpr int NW = HEAD ? kHeadWaves : kWaves;          // waves per workgroup
     __shared__ __attribute__((aligned(16))) float sm_w[2][kWBlock];   // MnT, Wv (zero padded; widx layout)
     // HEAD: up to 128 output classes as split-bf16 A fragments, [hi | lo][(blk * 4 + ft) * 2 + kb][lane]: lane (lg, l15) holds
@@ -926,7 +951,8 @@ void simple_layer_kernel(LayerArgsT<T> a) {
         GatherCursor gc;
         if (GATHER) gc = gather_begin(a.g_rowptr, a.g_src, a.g_val, row, row_ok);
         f32x4 xa[4];
-        load_rows<G>(xa, a.x, a.ldx, row, a.n_rows, lg, C);
+        if constexpr (SC) load_slices<G>(xa, reinterpret_cast<const f32x4*>(a.x), a.ldx, a.rscale, row, a.n_rows, lg, C);
+        else load_rows<G>(xa, a.x, a.ldx, row, a.n_rows, lg, C);
         // denominator of this lane's row: x.u + cd, folded over the four lane groups
         float den = 0.f;
 #pragma unroll
@@ -1144,16 +1170,17 @@ extern "C" int dif_gram_f32(const float* x, int64_t ldx, int64_t n_rows, int C, 
 }
 
 // Input layer (Linear -> LayerNorm -> ReLU, C_in <= 64 -> D <= 64, D % 4 == 0) + Gram record of its OUTPUT + slice-major copy
-// (ys / rowptr / plan nullable together) in one pass; out [n_rows, D] row-major.  workspace: dif_gram_workspace_bytes(n_rows, D).
+// (ys / rowptr / plan nullable together) in one pass; out [n_rows, D] row-major -- or NULL with ys given (single copy: the
+// hidden rows are left as the slice-major copy alone, nothing is written through out).  workspace: dif_gram_workspace_bytes(n_rows, D).
 extern "C" int dif_input_gram_f32(const float* x, int64_t ldx, int64_t n_rows, int C_in, const float* W, const float* bias, int D,
                                   const float* ln_weight, const float* ln_bias, float ln_eps, int relu, float* out, int64_t ldo,
                                   const int32_t* rowptr, const int32_t* plan, float* ys, float* record, void* workspace,
                                   size_t workspace_bytes, dif_stream_t stream) {
-    DIF_REQUIRE(x && W && bias && out && record && workspace && n_rows > 0, DIF_E_BADARG, "dif_input_gram: null pointer or no rows");
+    DIF_REQUIRE(x && W && bias && (out || ys) && record && workspace && n_rows > 0, DIF_E_BADARG, "dif_input_gram: null pointer or no rows");
     DIF_REQUIRE(C_in > 0 && C_in <= 64 && D > 0 && D <= 64 && D % 4 == 0, DIF_E_SHAPE,
                 "dif_input_gram: covers C_in <= 64 -> D <= 64, D %% 4 == 0 (got %d -> %d)", C_in, D);
     DIF_REQUIRE((ln_weight == nullptr) == (ln_bias == nullptr), DIF_E_BADARG, "dif_input_gram: ln_weight and ln_bias must be given together");
-    DIF_REQUIRE(ldx >= C_in && ldo >= D && ldo % 4 == 0 && dif::aligned16(out), DIF_E_BADARG,
+    DIF_REQUIRE(ldx >= C_in && (!out || (ldo >= D && ldo % 4 == 0 && dif::aligned16(out))), DIF_E_BADARG,
                 "dif_input_gram: rows of out must be 16-byte aligned, leading dimensions >= the row lengths");
     DIF_REQUIRE(workspace_bytes >= dif_gram_workspace_bytes(n_rows, D), DIF_E_WORKSPACE, "dif_input_gram: workspace too small");
     DIF_REQUIRE((ys == nullptr) || (rowptr && plan && dif::aligned16(ys)), DIF_E_BADARG,
@@ -1169,10 +1196,12 @@ extern "C" int dif_input_gram_f32(const float* x, int64_t ldx, int64_t n_rows, i
     float* ws = static_cast<float*>(workspace);
     const int xvec = (C_in % 4 == 0) && (ldx % 4 == 0) && dif::aligned16(x);
     const int kq = (C_in + 15) / 16;
-#define DIF_IG(KQ) hipLaunchKernelGGL((input_gram_kernel<KQ>), dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx, n_rows, C_in, W, bias, D, \
-                                      ln_weight, ln_bias, ln_eps, relu, out, ldo, rowptr, reinterpret_cast<f32x4*>(ys), npad, ws, rec, xvec)
+#define DIF_IG2(KQ, ROWS) hipLaunchKernelGGL((input_gram_kernel<KQ, ROWS>), dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx, n_rows, C_in, W, bias, D, \
+                                             ln_weight, ln_bias, ln_eps, relu, out, ldo, rowptr, reinterpret_cast<f32x4*>(ys), npad, ws, rec, xvec)
+#define DIF_IG(KQ) do { if (out) DIF_IG2(KQ, true); else DIF_IG2(KQ, false); } while (0)
     if (kq == 1) DIF_IG(1); else if (kq == 2) DIF_IG(2); else if (kq == 3) DIF_IG(3); else DIF_IG(4);
 #undef DIF_IG
+#undef DIF_IG2
     if (int rc = dif::launch_status("input_gram_kernel")) return rc;
     return dif::launch_record_finalize(ws, P, rec, D * D + D, 0, record, st);
 }
@@ -1435,14 +1464,18 @@ int layer_entry(const T* x, int64_t ldx, int64_t n_rows, int C, int D, const flo
                 int64_t ldo, const int32_t* rowptr, const int32_t* plan, float* next_ys, dif_stream_t stream,
                 const float* Wo = nullptr, const float* bo = nullptr, int Co = 0,
                 T* logits = nullptr, int64_t ldl = 0, const int32_t* g_rowptr = nullptr, const int32_t* g_src = nullptr,
-                const float* g_val = nullptr) {
+                const float* g_val = nullptr, const float* rscale = nullptr) {
     const bool head = Wo != nullptr;
-    DIF_REQUIRE(x && coef && (out || head) && n_rows > 0, DIF_E_BADARG, "dif_simple_layer: null pointer or no rows");
+    const bool sc = rscale != nullptr;             // x is the slice-major pre-scaled copy, ldx its rows per slice
+    DIF_REQUIRE(x && coef && (out || head || (sc && next_ys)) && n_rows > 0, DIF_E_BADARG, "dif_simple_layer: null pointer or no rows");
+    DIF_REQUIRE(!sc || (std::is_same<T, float>::value && !g_rowptr && ldx >= n_rows && dif::aligned16(x)), DIF_E_BADARG,
+                "dif_simple_layer: rscale (slice-major input) needs float32 rows, ldx = rows per slice >= n_rows, a 16-byte "
+                "aligned copy and no in-kernel aggregation");
     DIF_REQUIRE(!head || (bo && logits && Co > 0 && Co <= 128 && ldl >= Co && !next_ys), DIF_E_BADARG,
                 "dif_simple_layer: the fused output Linear needs bo, logits, 1 <= Co <= 128, ldl >= Co, no next-layer products");
     DIF_REQUIRE(C > 0 && C <= 64 && C % 4 == 0 && D > 0 && D <= 64, DIF_E_SHAPE,
                 "dif_simple_layer: covers C <= 64 (C %% 4 == 0) and D <= 64 (got %d, %d)", C, D);
-    DIF_REQUIRE(ldx >= C && ldx % 4 == 0 && dif::aligned_v4<T>(x) && (!out || ldo >= D), DIF_E_BADARG,
+    DIF_REQUIRE((sc || (ldx >= C && ldx % 4 == 0)) && dif::aligned_v4<T>(x) && (!out || ldo >= D), DIF_E_BADARG,
                 "dif_simple_layer: rows of x must be aligned to 4 elements, ldo >= D");
     DIF_REQUIRE((!out || dif::aligned_v4<T>(out)) && (!x0 || dif::aligned_v4<T>(x0)) && (!logits || dif::aligned_v4<T>(logits)),
                 DIF_E_BADARG, "dif_simple_layer: out / x0 / logits must be aligned to 4 elements");
@@ -1469,13 +1502,25 @@ int layer_entry(const T* x, int64_t ldx, int64_t n_rows, int C, int D, const flo
                 "dif_simple_layer: the in-kernel aggregation takes rowptr, src AND val, no ax and no next-layer products");
     LayerArgsT<T> a = {x, ldx, ax, ldax, coef, Wv, bv, row_sums, gcn_scale, x0, ldx0, residual, alpha, ln_weight, ln_bias, ln_eps,
                        relu, out, ldo, n_rows, C, D, rowptr, reinterpret_cast<f32x4*>(next_ys), npad, Wo, bo, Co, logits, ldl,
-                       g_rowptr, g_src, g_val};
+                       g_rowptr, g_src, g_val, rscale};
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool exact = C == 64 && D == 64 && ldo % 4 == 0 && (!x0 || ldx0 % 4 == 0);
     const bool gw = (ax != nullptr || gather) && Wv != nullptr;
     // dense 64 x 64 float32 layers (the headline shape): both products on split-bfloat16 operands unless DIFFORMER_EXACT_FP32=1
     const bool split = exact && f32 && !gather && !dif::exact_fp32() &&
                        (reinterpret_cast<uintptr_t>(coef) & 15u) == 0 && (!gw || (reinterpret_cast<uintptr_t>(Wv) & 15u) == 0);
+    if (sc) {
+        // slice-major input: the split-bf16 kernels at 64 x 64, the general (guarded) kernel for every other shape
+        if constexpr (std::is_same<T, float>::value) {
+#define DIF_LAYER_SC(E, G, H, S) hipLaunchKernelGGL((simple_layer_kernel<E, G, T, H, false, S, true>), dim3(P), dim3(64 * (H ? kHeadWaves : kWaves)), 0, st, a)
+#define DIF_LAYER_SC2(E, S) do { if (head) { if (gw) DIF_LAYER_SC(E, true, true, S); else DIF_LAYER_SC(E, false, true, S); } \
+                                 else { if (gw) DIF_LAYER_SC(E, true, false, S); else DIF_LAYER_SC(E, false, false, S); } } while (0)
+            if (split) DIF_LAYER_SC2(true, true); else DIF_LAYER_SC2(false, false);
+#undef DIF_LAYER_SC2
+#undef DIF_LAYER_SC
+        }
+        return dif::launch_status("simple_layer_kernel");
+    }
     if (split) {
         if constexpr (std::is_same<T, float>::value) {
             if (head) {
@@ -1508,9 +1553,10 @@ extern "C" int dif_simple_layer_f32(const float* x, int64_t ldx, int64_t n_rows,
                                     float gcn_scale, const float* x0, int64_t ldx0, int residual, float alpha,
                                     const float* ln_weight, const float* ln_bias, float ln_eps, int relu, float* out,
                                     int64_t ldo, const int32_t* rowptr, const int32_t* plan, float* next_ys,
-                                    dif_stream_t stream) {
+                                    const float* rscale, dif_stream_t stream) {
     return layer_entry<float>(x, ldx, n_rows, C, D, coef, ax, ldax, Wv, bv, row_sums, gcn_scale, x0, ldx0, residual, alpha,
-                              ln_weight, ln_bias, ln_eps, relu, out, ldo, rowptr, plan, next_ys, stream);
+                              ln_weight, ln_bias, ln_eps, relu, out, ldo, rowptr, plan, next_ys, stream,
+                              nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, rscale);
 }
 
 // The LAST layer of a model with the output Linear of difformer.py:208 in the same pass: logits [n, Co] = out Wo^T + bo
@@ -1520,11 +1566,11 @@ extern "C" int dif_simple_layer_head_f32(const float* x, int64_t ldx, int64_t n_
                                          const float* row_sums, float gcn_scale, const float* x0, int64_t ldx0, int residual,
                                          float alpha, const float* ln_weight, const float* ln_bias, float ln_eps, int relu,
                                          float* out, int64_t ldo, const float* Wo, const float* bo, int Co, float* logits,
-                                         int64_t ldl, dif_stream_t stream) {
+                                         int64_t ldl, const float* rscale, dif_stream_t stream) {
     DIF_REQUIRE(Wo != nullptr, DIF_E_BADARG, "dif_simple_layer_head_f32: Wo is null");
     return layer_entry<float>(x, ldx, n_rows, C, D, coef, ax, ldax, Wv, bv, row_sums, gcn_scale, x0, ldx0, residual, alpha,
                               ln_weight, ln_bias, ln_eps, relu, out, ldo, nullptr, nullptr, nullptr, stream,
-                              Wo, bo, Co, logits, ldl);
+                              Wo, bo, Co, logits, ldl, nullptr, nullptr, nullptr, rscale);
 }
 
 // The layer with the AGGREGATION in the same pass (graphs with a few entries per row, single GPU): instead of ax the kernel

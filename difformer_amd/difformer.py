@@ -410,6 +410,7 @@ class DIFFormer(nn.Module):
         self.alpha = alpha
         self.auto_graph = True     # repeated inference forwards over the same operands replay as one hipGraph (_forward_graphed)
         self._ag_state = None
+        self.last_single_copy = 0  # layer kernels of the last eager forward that read their rows from the slice-major copy alone
 
     def __getstate__(self):
         # copy.deepcopy(model) for a best-checkpoint / EMA copy and torch.save(model) must keep working after eval calls:
@@ -467,6 +468,25 @@ class DIFFormer(nn.Module):
         x = ag.linear(x, self.fcs[0].weight, self.fcs[0].bias, *_ln_args(bn), relu=True)
         return F.dropout(x, p=self.dropout, training=training)
 
+    def _single_copy(self, x, hidden, csr):
+        """True when every reader of the hidden rows in this forward is a closed-form layer kernel over the same dense graph,
+        so that the rows may exist ONCE, as the slice-major copy the sliced product reads (ops.LayerChain.single_copy; the
+        layers choose per call).  That needs: inference; every layer on the `closed_narrow` route at hidden -> hidden with
+        the graph term, without use_source (layer_[0] would have to exist row-major) and without a row shard; the background
+        coefficient chain (it reads the rows beside the product); a graph whose rows can be recovered from the copy
+        (GraphCSR.row_scale: every node has an incoming entry); neither DIFFORMER_SINGLE_COPY=0 nor DIFFORMER_EXACT_FP32=1."""
+        if (not ops.SINGLE_COPY or not ops.SIDE_CHAIN or ops.EXACT_FP32 or self.training or not len(self.convs) or
+                not hasattr(ops.get_backend(), "coeffs_bg")):
+            return False
+        probe = x.new_empty(1).expand(x.shape[0], hidden)               # what the route looks at: shape, dtype, no gradient
+        for i, conv in enumerate(self.convs):
+            if conv.use_source or not conv.use_graph or conv.row_shard is not None or conv.out_channels != hidden:
+                return False
+            ln = _ln_args(self.bns[i + 1] if self.use_bn else None)
+            if conv._route(probe, probe, None, None, probe if self.residual else None, ln[0], ln[1], False) != "closed_narrow":
+                return False
+        return csr.row_scale() is not None
+
     def _input_with_products(self, x, edge_index, edge_weight, conv0):
         """Narrow input features in front of a closed-form first layer on a dense graph (BASELINE config C4: 8 -> 64): the
         input layer's kernel also leaves the Gram record of its output and the slice-major copy the sliced product reads
@@ -489,6 +509,10 @@ class DIFFormer(nn.Module):
         sl = csr.sliced(0, x.shape[0], hidden) if x.shape[0] == csr.num_nodes else None
         if sl is None:
             return None
+        if self._single_copy(x, hidden, csr):                  # the hidden rows are left as the slice-major copy alone
+            _, record, ys = be.input_gram(x, fc.weight, fc.bias, bn.weight, bn.bias, bn.eps, True, csr.rowptr, sl.plan, rows=False)
+            h = ops.rows_stand_in(ys, x.shape[0], hidden)
+            return h, dict(x=h, sl=sl, record=record, ys=ys, rscale=csr.row_scale())
         h, record, ys = be.input_gram(x, fc.weight, fc.bias, bn.weight, bn.bias, bn.eps, True, csr.rowptr, sl.plan)
         return h, dict(x=h, sl=sl, record=record, ys=ys)
 
@@ -511,7 +535,7 @@ class DIFFormer(nn.Module):
         if len(convs) * (4.0 * x.shape[0] * hidden * x.element_size() + 8.0 * nnz) > _AUTO_GRAPH_MAX_BYTES:
             return None                  # GPU-bound: nothing to gain from a replay, gigabytes to hold for it
         key = [x.data_ptr(), x.shape, x.stride(), x.dtype, torch.cuda.current_stream(x.device).cuda_stream,
-               self.alpha, self.use_bn, self.residual, ops.SIDE_CHAIN, ops.EXACT_FP32, len(convs)]
+               self.alpha, self.use_bn, self.residual, ops.SIDE_CHAIN, ops.EXACT_FP32, ops.SINGLE_COPY, len(convs)]
         lin = []
         for m in mods["fcs"]._modules.values():
             lin.append(m)
@@ -607,6 +631,7 @@ class DIFFormer(nn.Module):
         first = self._input_with_products(x, edge_index, edge_weight, conv0)
         if first is not None:                                  # :188-192 and the first layer's Gram record / SpMM operand
             x, carry.products = first
+            carry.single_copy = carry.products.get("rscale") is not None
         else:
             x = self._input_layer(x, self.training)            # difformer.py:188-192
         layer_.append(x)
@@ -625,6 +650,7 @@ class DIFFormer(nn.Module):
             if self.training:
                 x = F.dropout(x, p=self.dropout, training=True)
             layer_.append(x)
+        self.last_single_copy = carry.single           # layer kernels of this forward that read the slice-major copy (0: two-copy path)
         out = x if carry.head_done else ag.linear(x, self.fcs[-1].weight, self.fcs[-1].bias)   # :208
         return out[mix.inv] if mix is not None else out
 

@@ -266,6 +266,7 @@ class GraphCSR:
         self.dinv = None            # adjoint CSR only: deg^-1/2 of the FORWARD graph (its own row lengths are out-degrees)
         self._sliced = {}           # (row_begin, n_rows, F) -> SlicedAdjacency | None
         self._row_sums = None
+        self._row_scale = False      # not computed yet (None = this graph has none: row_scale)
         self._format_checked = False # csr_cache.get(build_format=True) has built (or ruled out) the sliced format for this CSR
         self.weight_scale = 1.0      # a CONSTANT edge_weight (every entry equal: `--special_treat dense` / knn, spatial-temporal/
                                      # main.py:99,103) is not in `val`: the CSR is the unweighted one and every caller multiplies
@@ -353,6 +354,20 @@ class GraphCSR:
             ones = torch.ones((self.num_nodes, 4), dtype=torch.float32, device=self.rowptr.device)
             self._row_sums = _aggregate_rows(get_backend(), self, None, ones, 0, self.num_nodes)[:, 0].contiguous()
         return self._row_sums
+
+    def row_scale(self):
+        """rscale = deg^1/2 (float32 [N]), the inverse of the deg^-1/2 the slice-major copy of the sliced product is scaled
+        by: with it a closed-form layer recovers its input rows from that copy, x[r] = ys[r] * rscale[r], and the rows need
+        no row-major copy (single-copy mode of simple_layer_closed_form).  None when a row cannot be recovered -- some node
+        has no incoming entry (deg = 0: its ys row is zero whatever x was) -- or the product does not factor this way
+        (edge weights, an adjoint CSR).  One pass over rowptr and one host read per graph, kept with the CSR."""
+        if self._row_scale is False:
+            self._row_scale = None
+            if not self.weighted and not self.transposed and self.num_nodes > 0 and self.nnz > 0:
+                deg = self.rowptr[1:] - self.rowptr[:-1]
+                if int(deg.min()) > 0:                     # cold path: once per graph
+                    self._row_scale = deg.to(torch.float32).sqrt().contiguous()
+        return self._row_scale
 
     def max_degree(self):
         """Longest row (entries).  `build` gets it from the CSR kernels with the host read a build has anyway
@@ -679,6 +694,9 @@ def side_stream(dev):
 
 
 SIDE_CHAIN = os.environ.get("DIFFORMER_SIDE_CHAIN", "1") != "0"
+# DIFFORMER_SINGLE_COPY=0: every closed-form layer keeps its rows row-major AND slice-major (the two-copy path), as before the
+# single-copy mode existed -- same kernels, same bits.
+SINGLE_COPY = os.environ.get("DIFFORMER_SINGLE_COPY", "1") != "0"
 # DIFFORMER_EXACT_FP32=1: no product of the forward runs on split-bfloat16 operands -- the long-row input Linear takes the
 # fp32 MFMA (the library reads the same variable), and the output Linear is not folded into the last layer kernel (whose
 # extra product is a split-bfloat16 one) but runs as its own fp32-MFMA launch.  Results move by ~4e-6 of the logits' scale.
@@ -725,15 +743,29 @@ class LayerChain:
                          and / or their slice-major copy `ys` for the sliced format `sl`.  Left by
                          DIFFormer._input_with_products and by a layer kernel asked through `want_next`; consumed by the
                          next simple_layer_closed_form, which clears it whether it could use it or not.
+                         Single copy: the dict also has rscale (GraphCSR.row_scale) and `x` is only a stand-in
+                         (rows_stand_in): the rows exist as ys alone and the next layer reads them from there.
+        single_copy in.  Set once by the model loop (DIFFormer._single_copy): every reader of the layers' rows in this forward
+                         is a closed-form layer kernel over the same dense graph, so a layer asked through `want_next` may
+                         leave its rows as the slice-major copy alone.  simple_layer_closed_form chooses the mode per layer.
+        single     out.  How many layer kernels of this forward read their input from the slice-major copy.
         head_done  out.  Set by DIFFormerConv._closed_narrow once `head` was applied: the layer's output is the model's
                          logits already.  Read by the model loop after the last layer."""
 
     def __init__(self, want_next=False, head=None, products=None):
         self.want_next, self.head, self.products, self.head_done = want_next, head, products, False
+        self.single_copy, self.single = False, 0
+
+
+def rows_stand_in(ys, n, C):
+    """What a single-copy layer returns in place of its rows: a float32 [n, C] view of ONE element (strides 0) on the rows'
+    device.  It carries what the routing looks at (shape, dtype, device, identity) and no data: the rows are in `ys`, and only
+    the simple_layer_closed_form that finds them in LayerChain.products may consume them -- any other call is refused there."""
+    return ys.new_empty(1).expand(n, C)
 
 
 def _simple_layer_kernel(be, x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu,
-                         next_operand=None, head=None, gather=None):
+                         next_operand=None, head=None, gather=None, rscale=None, rows=True):
     """The layer kernel of the closed form: the one be.simple_layer call.  Optional: next_operand = (rowptr, plan) -> the
     kernel also returns the slice-major copy of its output; head = (weight, bias) of the model's output Linear -> logits;
     gather = (rowptr, src, val) -> the kernel aggregates by itself.  Only the ones that are set are passed, so a stand-in
@@ -745,6 +777,10 @@ def _simple_layer_kernel(be, x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual
         optional["head"] = head
     if gather is not None:
         optional["gather"] = gather
+    if rscale is not None:                         # single copy: x is the slice-major copy of the rows
+        optional["rscale"] = rscale
+    if not rows:
+        optional["rows"] = False
     return be.simple_layer(x, coef, D, ax, Wv, bv, rs, gcn_scale, x0, residual, alpha, ln_weight, ln_bias, eps, relu, **optional)
 
 
@@ -783,6 +819,7 @@ def _record_and_coeffs(be, x, proj, csr, sl, have, shard, factors, attn_scale):
     n_global = shard.n_global if sharded else n
     record = have["record"] if have is not None else None
     ys = have["ys"] if have is not None else None
+    rscale = have.get("rscale") if have is not None else None      # single copy: x is a stand-in, the rows are ys * rscale
     # With the sliced product ahead (0.3 ms that does not need the coefficients) the chain Gram -> coefficients runs as
     # single-wave background kernels on a second stream, UNDER the product (csrc/side_chain.hip).
     if (SIDE_CHAIN and factors is not None and sl is not None and not sharded and x.dtype == torch.float32 and
@@ -796,12 +833,17 @@ def _record_and_coeffs(be, x, proj, csr, sl, have, shard, factors, attn_scale):
             # ... but is ENQUEUED after the product: its workgroups then take the wave slot the product leaves free on
             # every CU instead of delaying the product's start
             with torch.cuda.stream(side):
+                if record is None and rscale is not None:
+                    return be.coeffs_bg(ys, None, n_global, factors, C, D, attn_scale, rscale=rscale)
                 return be.coeffs_bg(None if record is not None else x, record, n_global, factors, C, D, attn_scale)
 
         def join(coef):                            # the layer kernel needs the coefficients: the side stream joins
             main.wait_stream(side)
             coef.record_stream(main)
         return record, ys, None, (enqueue, join)
+    if rscale is not None:
+        raise RuntimeError("difformer_amd: rows kept as their slice-major copy alone need the background coefficient chain "
+                           "(DIFFORMER_SIDE_CHAIN=0 and DIFFORMER_SINGLE_COPY=1 do not go together)")
     need_ys = sl is not None and ys is None and not sharded
     if (record is None and not need_ys and not sharded and x.dtype == torch.float32 and C % 4 == 0 and
             n <= GRAM_COEFFS_MAX_ROWS and hasattr(be, "gram_coeffs")):
@@ -873,7 +915,12 @@ def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_sca
     handle = shard.all_gather_rows_async(x) if (sharded and csr is not None) else None
     have = carry.products if (carry is not None and not sharded) else None
     if have is not None and not (have["x"] is x and have["sl"] is sl):
+        if have["x"] is x and have.get("rscale") is not None:
+            raise RuntimeError("difformer_amd: these rows exist as a slice-major copy for another sliced format only")
         have = None
+    rscale = have.get("rscale") if have is not None else None      # single copy in: x is rows_stand_in, the rows are have["ys"]
+    if rscale is not None and (x0 is not None or keep is not None or have["ys"] is None or sl is None):
+        raise RuntimeError("difformer_amd: rows kept as their slice-major copy alone cannot feed this layer")
     record, ys, coef, side = _record_and_coeffs(be, x, (Wq, bq, Wk, bk, Wv, bv), csr, sl, have, shard, factors, attn_scale)
     ax, rs, gather, late = _graph_term(be, x, csr, sl, ys, handle, shard, gcn_scale, Wv is not None, keep is None,
                                        side[0] if side is not None else None)
@@ -888,11 +935,19 @@ def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_sca
         head = tuple(f32_param(t) for t in head)   # bfloat16 storage: exact float32 copies, as for the other parameters
     want_next = (carry is not None and not sharded and carry.want_next and D % 4 == 0 and D == C and
                  x.dtype == torch.float32 and sl is not None and head is None and gather is None)
-    out = _simple_layer_kernel(be, x, coef, D, ax, Wv, bv, rs, gcn_scale, *tail,
-                               next_operand=(csr.rowptr, sl.plan) if want_next else None, head=head, gather=gather)
+    # the mode: this layer's rows may exist as the slice-major copy alone when the model loop has said that only closed-form
+    # layer kernels over this graph read them (carry.single_copy) and the graph lets a row be recovered from the copy
+    rscale_out = csr.row_scale() if (want_next and carry.single_copy and SINGLE_COPY and side is not None) else None
+    out = _simple_layer_kernel(be, ys if rscale is not None else x, coef, D, ax, Wv, bv, rs, gcn_scale, *tail,
+                               next_operand=(csr.rowptr, sl.plan) if want_next else None, head=head, gather=gather,
+                               rscale=rscale, rows=rscale_out is None)
+    if rscale is not None:
+        carry.single += 1
     if want_next:
         out, ys2 = out
-        carry.products = dict(x=out, sl=sl, record=None, ys=ys2)
+        if out is None:
+            out = rows_stand_in(ys2, n, D)
+        carry.products = dict(x=out, sl=sl, record=None, ys=ys2, rscale=rscale_out)
     return out
 
 

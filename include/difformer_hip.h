@@ -37,7 +37,9 @@ extern "C" {
 
 #define DIF_ABI_VERSION 3   /* 2: dif_csr_build's status is int32[2] (status[1] = longest row): a caller that allocates one int must be rebuilt
                                3: dif_simple_layer_f32 no longer writes the next layer's Gram record (its record and
-                                  workspace parameters are gone); dif_wide_coeffs_f64 is the only wide-coefficient entry point */
+                                  workspace parameters are gone); dif_wide_coeffs_f64 is the only wide-coefficient entry point;
+                                  dif_simple_layer_f32, dif_simple_layer_head_f32 and dif_gram_bg_f32 take `rscale` in front
+                                  of the stream (NULL: as before) */
 
 #define DIF_E_BADARG   (-1)  /* null pointer, non-positive size, misaligned pointer */
 #define DIF_E_SHAPE    (-2)  /* shape the kernels do not cover */
@@ -261,6 +263,11 @@ int dif_row_order(const int32_t* rowptr, int64_t row_begin, int64_t n_rows, int3
  *                          (NULL when bv is not needed); residual = 0 skips the alpha mix, ln_weight = NULL the LayerNorm.
  *                          next_ys != NULL: the pass also writes the slice-major copy of `out` scaled by deg^-1/2 (what
  *                          dif_gram_f32 would write for the next layer), 256 contiguous bytes per lane group.
+ *                          rscale != NULL (single copy; float32, every node with an incoming entry): x is not the row-major
+ *                          layer input but its slice-major copy ys = deg^-1/2 x, float[C/4][ldx][4] with ldx = rows per slice
+ *                          (>= n_rows), as dif_gram_f32 / dif_input_gram_f32 / a previous layer left it, and rscale
+ *                          float[n_rows] = deg^1/2 recovers the row, x[r] = ys[r] * rscale[r] (2 ulp).  out may then be NULL
+ *                          when next_ys is given: the finished rows are left as the slice-major copy alone.
  * ------------------------------------------------------------------------------------- */
 size_t dif_gram_workspace_bytes(int64_t n_rows, int C);
 int dif_gram_f32(const float* x, int64_t ldx, int64_t n_rows, int C, const int32_t* rowptr, const int32_t* plan,
@@ -281,7 +288,8 @@ int dif_simple_layer_f32(const float* x, int64_t ldx, int64_t n_rows, int C, int
                          const float* ax, int64_t ldax, const float* Wv, const float* bv, const float* row_sums,
                          float gcn_scale, const float* x0, int64_t ldx0, int residual, float alpha,
                          const float* ln_weight, const float* ln_bias, float ln_eps, int relu, float* out,
-                         int64_t ldo, const int32_t* rowptr, const int32_t* plan, float* next_ys, dif_stream_t stream);
+                         int64_t ldo, const int32_t* rowptr, const int32_t* plan, float* next_ys, const float* rscale,
+                         dif_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * a3, dense graphs without edge weights: feature-sliced product with the source rows staged in LDS
@@ -467,19 +475,21 @@ int dif_simple_layer_head_f32(const float* x, int64_t ldx, int64_t n_rows, int C
                               float gcn_scale, const float* x0, int64_t ldx0, int residual, float alpha,
                               const float* ln_weight, const float* ln_bias, float ln_eps, int relu, float* out,
                               int64_t ldo, const float* Wo, const float* bo, int Co, float* logits, int64_t ldl,
-                              dif_stream_t stream);
+                              const float* rscale, dif_stream_t stream);
 /* The coefficient chain of the closed form as BACKGROUND kernels (csrc/side_chain.hip): single-wave workgroups without LDS,
  * the footprint that fits beside a workgroup of the feature-sliced product, so that on a second stream the chain runs
  * under the product instead of in front of it (neither depends on the other).  Augmented formulation: X~ = [X | 1],
  * W~ = [W | b]; all matrices float[80 * 80], zero padded, augmented index 64.
  *   dif_gram_bg_f32          gt float[80 * 80 + 400] = G~ = [[X^T X, sum x], [sum x^T, n_global]] from one pass over x, followed
  *                            by 100 float64 pairs of partial norm products <st, G~> (x == NULL: `workspace` holds one
- *                            finished record [X^T X | sum x], e.g. dif_gram_f32's, and is only re-laid)
+ *                            finished record [X^T X | sum x], e.g. dif_gram_f32's, and is only re-laid).  rscale != NULL:
+ *                            x is the slice-major copy deg^-1/2 x (ldx = rows per slice) and rscale float[n_rows] = deg^1/2,
+ *                            as for dif_simple_layer_f32
  *   dif_simple_coeffs_bg_f32 coef (layout of dif_simple_coeffs_f32) from gt and the weight-only factors
  *                            pt = W~q^T W~k, vtt = [W~v^T | e]^T, st = [W~q^T W~q ; W~k^T W~k]; scratch float[80 * 80 + 4]. */
 size_t dif_gram_bg_workspace_bytes(int64_t n_rows, int C);
 int dif_gram_bg_f32(const float* x, int64_t ldx, int64_t n_rows, int C, int64_t n_global, const float* st, float* gt,
-                    void* workspace, size_t workspace_bytes, dif_stream_t stream);
+                    void* workspace, size_t workspace_bytes, const float* rscale, dif_stream_t stream);
 int dif_simple_coeffs_bg_f32(const float* gt, const float* pt, const float* vtt, const float* st, int C, int D,
                              float attn_scale, float* scratch, float* coef, dif_stream_t stream);
 /* Gram record of that closed form: record float[dif_simple_reduced_len(1, C, C)] = [X^T X (C x C, row-major) | sum x (C) |
@@ -641,7 +651,8 @@ int dif_gram_bf16(const void* x, int64_t ldx, int64_t n_rows, int C, float* reco
 /* Input layer + Gram record + slice-major copy in one pass (difformer.py:188-191 feeding the first closed-form layer on a
  * dense graph): out = ReLU(LayerNorm(x W^T + b)) [n_rows, D] row-major for C_in <= 64 -> D <= 64 (D % 4 == 0), record =
  * [out^T out | column sums] as dif_gram_f32 leaves it, ys (nullable with rowptr / plan) = the deg^-1/2-scaled slice-major
- * copy the sliced product reads.  workspace: dif_gram_workspace_bytes(n_rows, D). */
+ * copy the sliced product reads.  out may be NULL when ys is given (single copy: the hidden rows exist as ys alone).
+ * workspace: dif_gram_workspace_bytes(n_rows, D). */
 int dif_input_gram_f32(const float* x, int64_t ldx, int64_t n_rows, int C_in, const float* W, const float* bias, int D,
                        const float* ln_weight, const float* ln_bias, float ln_eps, int relu, float* out, int64_t ldo,
                        const int32_t* rowptr, const int32_t* plan, float* ys, float* record, void* workspace,
