@@ -13,6 +13,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DIFFORMER_HIP_LIB: another build of the SAME ABI (A/B kernel experiments); the default is the in-tree build
 LIB_PATH = os.environ.get("DIFFORMER_HIP_LIB") or os.path.join(_HERE, "lib", "libdifformer_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_hip.h"))
+# the attention-map library (C ABI: include/difformer_maps.h), loaded on first use by load_maps()
+MAPS_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_maps.so")
+MAPS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_maps.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -109,7 +112,13 @@ class TinyCfg(ctypes.Structure):
 # name -> (restype, argtypes): include/difformer_hip.h is the only declaration of the entry points
 SIGNATURES = _prototypes(_code)
 
+# ... and include/difformer_maps.h of the second library's
+_maps_code = _read_header(MAPS_HEADER_PATH)
+MAPS_VERSION = _defines(_maps_code, "DIF_MAPS_VERSION")["DIF_MAPS_VERSION"]
+MAPS_SIGNATURES = _prototypes(_maps_code)
+
 _lib = None
+_maps = None
 
 
 class DifformerHipError(RuntimeError):
@@ -157,6 +166,38 @@ def load():
     _single_hip_runtime()
     _lib = lib
     return lib
+
+
+def load_maps():
+    """Load libdifformer_maps.so once (after the main library: one HIP runtime, checked there); same rules as load()."""
+    global _maps
+    if _maps is not None:
+        return _maps
+    load()
+    if not os.path.exists(MAPS_LIB_PATH):
+        raise ImportError(
+            f"difformer_amd: HIP extension not built ({MAPS_LIB_PATH} missing). Build it with "
+            "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C difformer_amd/csrc`. "
+            "There is no CPU / eager fallback.")
+    lib = ctypes.CDLL(MAPS_LIB_PATH)
+    for name, (res, args) in MAPS_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise ImportError(f"difformer_amd: {MAPS_LIB_PATH} does not export {name}; rebuild it") from e
+        fn.restype, fn.argtypes = res, args
+    ver = lib.dif_maps_version()
+    if ver != MAPS_VERSION:
+        raise ImportError(f"difformer_amd: version mismatch of {MAPS_LIB_PATH} (library {ver}, host {MAPS_VERSION}); rebuild")
+    _maps = lib
+    return lib
+
+
+def check_maps(rc, what):
+    """check() for a call into libdifformer_maps.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_maps().dif_maps_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 
 def check(rc, what):

@@ -203,12 +203,13 @@ class HipBackend:
         torch.cuda.synchronize()
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
-    def _call(self, label, symbol, dev, *args):
+    def _call(self, label, symbol, dev, *args, maps=False):
         """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
         a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
         `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
-        collection, operands on the current device -- adds nothing around the call."""
-        fn = getattr(self.lib, symbol)
+        collection, operands on the current device -- adds nothing around the call.  maps: `symbol` is one of
+        libdifformer_maps.so (include/difformer_maps.h), loaded on first use."""
+        fn = getattr(_lib.load_maps() if maps else self.lib, symbol)
         index = dev.index
         if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
             rc = fn(*args, _raw_stream(index) if _raw_stream is not None else _stream(dev))
@@ -216,7 +217,7 @@ class HipBackend:
             with _Timed(self, label, dev):
                 rc = fn(*args, _stream(dev))
         if rc != 0:
-            _lib.check(rc, symbol)
+            (_lib.check_maps if maps else _lib.check)(rc, symbol)
 
     # ---- a1 --------------------------------------------------------------------------------
     def simple_reduce(self, q, k, v):
@@ -346,6 +347,26 @@ class HipBackend:
             return out, den
         self._call("dif_sigmoid_attn_" + sfx, "dif_sigmoid_attn_" + sfx, dev, *head, _ptr(ws), ws_bytes)
         return out
+
+    # ---- attention maps (libdifformer_maps.so) --------------------------------------------------
+    def attn_topk(self, q, k, mode, topk):
+        """q [N,H,M], k [L,H,M] float32, M a multiple of 4 up to 512 -> (values float32, indices int32) [N,H,topk]: per
+        query row and head the `topk` largest s = q . k over the keys, descending, ties to the lower key (mode 0: value s;
+        mode 1: value sigma(s) / sum_l sigma(s)).  The [N, L] scores never exist (csrc/attn_topk.hip)."""
+        dev = _require_device(q, k)
+        _all_f32(q=q, k=k)
+        N, H, M = q.shape
+        L = k.shape[0]
+        q, ldq = _rows(q, H * M, align=True)
+        k, ldk = _rows(k, H * M, align=True)
+        maps = _lib.load_maps()
+        values = torch.empty((N, H, topk), dtype=torch.float32, device=dev)
+        indices = torch.empty((N, H, topk), dtype=torch.int32, device=dev)
+        ws_bytes = maps.dif_attn_topk_workspace_bytes(N, L, H, M, topk)
+        ws = _workspace(ws_bytes, dev, floor=16)
+        self._call("dif_attn_topk_f32", "dif_attn_topk_f32", dev, _ptr(q), ldq, _ptr(k), ldk, N, L, H, M, int(mode), int(topk),
+                   _ptr(values), _ptr(indices), _ptr(ws), ws_bytes, maps=True)
+        return values, indices
 
     def sigmoid_backward(self, q, k, v, out, den, g):
         """(dq, dk, dv) of the sigmoid kernel for fp32 q [N,H,M], k [L,H,M], v [L,H,D], out / g [N,H,D], den [N,H];

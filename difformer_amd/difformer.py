@@ -672,3 +672,34 @@ class DIFFormer(nn.Module):
             x = ag.layer_tail(c, None, layer_[i] if self.residual else None, self.alpha, *_ln_args(bn))
             layer_.append(x)
         return torch.stack(attentions, dim=0)
+
+    def top_attentions(self, x, k):
+        """Per layer, node and head the k keys a node attends to most: (values float32 [layers,N,H,k], indices int64
+        [layers,N,H,k]) = the k largest entries of every row of `get_attentions(x)`, descending, ties to the lower node
+        index -- from a sweep that never forms the [N, N] map (attention_maps.attention_topk), so it runs at the sizes
+        where get_attentions cannot.  Same layers as get_attentions (no graph term); outputs are detached."""
+        from .attention_maps import attention_topk
+        if any(conv.row_shard is not None for conv in self.convs):
+            raise NotImplementedError("difformer_amd: top_attentions of a row-sharded model is not implemented (every rank "
+                                      "holds the top-k over its own keys only)")
+        dev = staging.staging_device(self, (x,))
+        if dev is not None:      # model and x in host memory: the device twin's result, returned on the host
+            twin = staging.twin_of(self, dev)
+            twin.refresh(self)
+            values, indices = twin.module.top_attentions(staging.operands.get(x, dev), k)
+            return values.to(x.device), indices.to(x.device)
+        with torch.no_grad():
+            layer_, values, indices = [], [], []
+            x = self._input_layer(x, False)
+            layer_.append(x)
+            for i, conv in enumerate(self.convs):
+                q, kk, v = conv._project(x, x)
+                val, idx = attention_topk(q, kk, conv.kernel, k)
+                values.append(val)
+                indices.append(idx)
+                v_att = v if v.shape[1] == conv.num_heads else v.expand(-1, conv.num_heads, -1).contiguous()
+                c = full_attention_conv(q, kk, v_att, conv.kernel)
+                bn = self.bns[i + 1] if self.use_bn else None
+                x = ag.layer_tail(c, None, layer_[i] if self.residual else None, self.alpha, *_ln_args(bn))
+                layer_.append(x)
+            return torch.stack(values, dim=0), torch.stack(indices, dim=0)
