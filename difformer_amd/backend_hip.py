@@ -108,7 +108,8 @@ def _rows(t, width, align=False):
         return None, 0
     t, ld = _row_major(t, width)
     if align and (ld % 4 or t.data_ptr() % (4 * t.element_size())):
-        return t.contiguous(), width
+        # dense rows that merely start off the boundary (a slice of a flat buffer) are contiguous already: clone them
+        return (t.clone() if t.is_contiguous() else t.contiguous()), width
     return t, ld
 
 
@@ -839,8 +840,8 @@ class HipBackend:
             ldx = x.shape[1]                           # rows per slice
         else:
             x, ldx = _rows(x, C, align=True)
-        ax, ldax = _rows(ax, C)
-        x0, ldx0 = _rows(x0, D)
+        ax, ldax = _rows(ax, C, align=True)
+        x0, ldx0 = _rows(x0, D, align=True)
         Wv, bv, ln_weight, ln_bias = _contig(Wv, bv, ln_weight, ln_bias)
         Wo = bo = None
         Co = 0
@@ -1073,7 +1074,7 @@ class HipBackend:
                 rscale = _f32(rscale, "rscale").contiguous()
             else:
                 n = x.shape[0]
-                x, ldx = _row_major(x, C)
+                x, ldx = _rows(x, C, align=True)
             ws_bytes = self.lib.dif_gram_bg_workspace_bytes(n, C)
             ws = _workspace(ws_bytes, dev, floor=16)
             xp = x
@@ -1126,9 +1127,9 @@ class HipBackend:
         _all_f32(Z=Z, add=add, rs=rs, bv=bv, x0=x0, prev=prev)
         if not Z.is_contiguous() or ldz % 4:
             raise ValueError("difformer_amd: layer_tail_mix needs a contiguous Z with a row length that is a multiple of 4")
-        add, lda = _rows(add, D)
-        x0, ldx0 = _rows(x0, D)
-        prev, ldp = _rows(prev, D)
+        add, lda = _rows(add, D, align=True)
+        x0, ldx0 = _rows(x0, D, align=True)
+        prev, ldp = _rows(prev, D, align=True)
         ln_weight, ln_bias, rs, bv = _contig(ln_weight, ln_bias, rs, bv)
         out = torch.empty((n, D), dtype=torch.float32, device=dev)
         den_ptr = None if den_col is None else Z.data_ptr() + 4 * int(den_col)

@@ -191,6 +191,10 @@ def test_row_major_layout_helper():
         assert t.data_ptr() == view.data_ptr() and ld == view.stride(0)
         t, ld = _rows(view, 8, align=True)
         assert t.is_contiguous() and t.data_ptr() != view.data_ptr() and ld == 8 and torch.equal(t, view)
+    flat = base[1: 1 + 10 * 8].view(10, 8)                  # dense rows that start 4 bytes off: contiguous, and still copied
+    assert flat.is_contiguous() and _rows(flat, 8)[0].data_ptr() == flat.data_ptr()
+    t, ld = _rows(flat, 8, align=True)
+    assert t.data_ptr() != flat.data_ptr() and t.data_ptr() % 16 == 0 and ld == 8 and torch.equal(t, flat)
     # bfloat16 rows are judged against 4 elements = 8 bytes: a start 8 bytes off a 16-byte boundary is aligned, 2 bytes is not
     half = base.view(torch.bfloat16)[: 10 * 24].view(10, 24)
     assert half[:, 4:12].data_ptr() % 16 == 8
@@ -198,6 +202,63 @@ def test_row_major_layout_helper():
     assert t.data_ptr() == half[:, 4:12].data_ptr() and ld == 24
     t, ld = _rows(half[:, 1:9], 8, align=True)
     assert t.is_contiguous() and t.data_ptr() != half[:, 1:9].data_ptr() and ld == 8
+
+
+def test_closed_form_methods_hand_their_launchers_aligned_rows(monkeypatch):
+    """simple_layer (x, ax, x0), layer_tail_mix (add, x0, prev) and coeffs_bg (x): their launchers reject rows that do not
+    start on a 4-element boundary or whose ld is no multiple of 4 (csrc/simple_layer.hip layer_entry, csrc/layer_tail.hip
+    rows_ok, csrc/side_chain.hip dif_gram_bg_f32), so every such operand goes through _rows(align=True): an aligned strided
+    view is passed as it is, any other view as a dense copy.  Asserted on the pointer and ld each method passes."""
+    import types
+    from difformer_amd import backend_hip
+    be = backend_hip.HipBackend()                            # loads the .so: fine without a GPU
+    calls = []
+    monkeypatch.setattr(backend_hip, "_require_device", lambda *tensors: torch.device("cpu"))
+    monkeypatch.setattr(be, "_call", lambda label, symbol, dev, *args, **kw: calls.append((symbol, args)))
+    n, C = 10, 8
+    base = torch.randn(4 * 64 + 64)
+    base = base[(-base.data_ptr() // 4) % 4:]
+    assert base.data_ptr() % 16 == 0
+    wide = base[: n * 24].view(n, 24)
+    views = {"aligned": wide[:, 8:16], "off1": wide[:, 1:9], "ld1": base[: n * 21].view(n, 21)[:, :8],
+             "dense off1": base[1: 1 + n * C].view(n, C)}
+    dense = torch.randn(n, C)
+    coef = torch.randn(be.lib.dif_simple_coeffs_len(C, C))
+    Z = torch.randn(n, C + 4)
+    factors = types.SimpleNamespace(pt=torch.zeros(80 * 80), vtt=torch.zeros(80 * 80), st=torch.zeros(2 * 80 * 80))
+
+    def passed(kind, view, ptr, ld):
+        if kind == "aligned":
+            assert (ptr, ld) == (view.data_ptr(), 24), kind
+        else:
+            assert ptr != view.data_ptr() and ptr % 16 == 0 and ld == C, (kind, ptr % 16, ld)
+
+    for kind, view in views.items():
+        for slot in ("x", "ax", "x0"):                      # one operand at a time as the view, the others dense
+            ops = dict(x=dense, ax=dense, x0=dense)
+            ops[slot] = view
+            calls.clear()
+            be.simple_layer(ops["x"], coef, C, ax=ops["ax"], x0=ops["x0"])
+            (symbol, args), = calls
+            assert symbol == "dif_simple_layer_f32"
+            at = {"x": (0, 1), "ax": (6, 7), "x0": (12, 13)}
+            for name, (p, l) in at.items():
+                if name == slot:
+                    passed(kind, view, args[p], args[l])
+                else:
+                    assert (args[p], args[l]) == (dense.data_ptr(), C)
+        for slot in ("add", "x0", "prev"):
+            ops = dict(add=dense, x0=dense, prev=dense)
+            ops[slot] = view
+            calls.clear()
+            be.layer_tail_mix(Z, C, C, 1.0, ops["add"], 1.0, None, None, ops["x0"], ops["prev"], 0.5, None, None, 1e-5)
+            (symbol, args), = calls
+            assert symbol == "dif_layer_tail_mix_f32" and args[0] == Z.data_ptr() and args[1] == C + 4
+            passed(kind, view, *{"add": args[5:7], "x0": args[12:14], "prev": args[14:16]}[slot])
+        calls.clear()
+        be.coeffs_bg(view, None, n, factors, C, C, 1.0)
+        assert [s for s, _ in calls] == ["dif_gram_bg_f32", "dif_simple_coeffs_bg_f32"]
+        passed(kind, view, *calls[0][1][0:2])
 
 
 def test_cpu_operands_raise_without_fallback():
