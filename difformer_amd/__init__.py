@@ -5,16 +5,16 @@
     logits = model(x, edge_index)
 
 The arithmetic lives in lib/libdifformer_hip.so (hand-written gfx950 kernels, C ABI in
-include/difformer_hip.h) and, for the top-k attention maps, lib/libdifformer_maps.so
-(include/difformer_maps.h).  Importing this package does not load the library; the first operator
+include/difformer_hip.h) and, for the attention maps, lib/libdifformer_maps.so (top-k per row,
+include/difformer_maps.h) and lib/libdifformer_edges.so (at the edges of a graph, include/difformer_edges.h).  Importing this package does not load the library; the first operator
 call does, and fails loudly if it has not been built.
 """
-from .attention_maps import attention_topk  # noqa: F401
+from .attention_maps import attention_on_edges, attention_topk  # noqa: F401
 from .difformer import DIFFormer, DIFFormerConv, full_attention_conv, gcn_conv  # noqa: F401
 from .difformer_v2 import DIFFormer_v2, TransConv  # noqa: F401
 from .dist import RowShard  # noqa: F401
 from .graphs import GraphedForward, GraphedTrainStep, graphed_training  # noqa: F401
 
 __all__ = ["DIFFormer", "DIFFormerConv", "full_attention_conv", "gcn_conv", "DIFFormer_v2", "TransConv", "RowShard",
-           "GraphedForward", "GraphedTrainStep", "graphed_training", "attention_topk"]
+           "GraphedForward", "GraphedTrainStep", "graphed_training", "attention_topk", "attention_on_edges"]
 __version__ = "0.1.0"

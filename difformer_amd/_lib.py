@@ -16,6 +16,9 @@ HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_h
 # the attention-map library (C ABI: include/difformer_maps.h), loaded on first use by load_maps()
 MAPS_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_maps.so")
 MAPS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_maps.h"))
+# the edge-attention library (C ABI: include/difformer_edges.h), loaded on first use by load_edges()
+EDGES_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_edges.so")
+EDGES_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_edges.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -117,8 +120,14 @@ _maps_code = _read_header(MAPS_HEADER_PATH)
 MAPS_VERSION = _defines(_maps_code, "DIF_MAPS_VERSION")["DIF_MAPS_VERSION"]
 MAPS_SIGNATURES = _prototypes(_maps_code)
 
+# ... and include/difformer_edges.h of the third's
+_edges_code = _read_header(EDGES_HEADER_PATH)
+EDGES_VERSION = _defines(_edges_code, "DIF_EDGES_VERSION")["DIF_EDGES_VERSION"]
+EDGES_SIGNATURES = _prototypes(_edges_code)
+
 _lib = None
 _maps = None
+_edges = None
 
 
 class DifformerHipError(RuntimeError):
@@ -168,35 +177,54 @@ def load():
     return lib
 
 
-def load_maps():
-    """Load libdifformer_maps.so once (after the main library: one HIP runtime, checked there); same rules as load()."""
-    global _maps
-    if _maps is not None:
-        return _maps
+def _load_side(path, signatures, version_fn, version):
+    """One of the small libraries next to libdifformer_hip.so (after it: one HIP runtime, checked there); same rules as load()."""
     load()
-    if not os.path.exists(MAPS_LIB_PATH):
+    if not os.path.exists(path):
         raise ImportError(
-            f"difformer_amd: HIP extension not built ({MAPS_LIB_PATH} missing). Build it with "
+            f"difformer_amd: HIP extension not built ({path} missing). Build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C difformer_amd/csrc`. "
             "There is no CPU / eager fallback.")
-    lib = ctypes.CDLL(MAPS_LIB_PATH)
-    for name, (res, args) in MAPS_SIGNATURES.items():
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in signatures.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
-            raise ImportError(f"difformer_amd: {MAPS_LIB_PATH} does not export {name}; rebuild it") from e
+            raise ImportError(f"difformer_amd: {path} does not export {name}; rebuild it") from e
         fn.restype, fn.argtypes = res, args
-    ver = lib.dif_maps_version()
-    if ver != MAPS_VERSION:
-        raise ImportError(f"difformer_amd: version mismatch of {MAPS_LIB_PATH} (library {ver}, host {MAPS_VERSION}); rebuild")
-    _maps = lib
+    ver = getattr(lib, version_fn)()
+    if ver != version:
+        raise ImportError(f"difformer_amd: version mismatch of {path} (library {ver}, host {version}); rebuild")
     return lib
+
+
+def load_maps():
+    """Load libdifformer_maps.so once."""
+    global _maps
+    if _maps is None:
+        _maps = _load_side(MAPS_LIB_PATH, MAPS_SIGNATURES, "dif_maps_version", MAPS_VERSION)
+    return _maps
+
+
+def load_edges():
+    """Load libdifformer_edges.so once."""
+    global _edges
+    if _edges is None:
+        _edges = _load_side(EDGES_LIB_PATH, EDGES_SIGNATURES, "dif_edges_version", EDGES_VERSION)
+    return _edges
 
 
 def check_maps(rc, what):
     """check() for a call into libdifformer_maps.so: the message comes from that library."""
     if rc != 0:
         msg = load_maps().dif_maps_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
+
+
+def check_edges(rc, what):
+    """check() for a call into libdifformer_edges.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_edges().dif_edges_last_error()
         raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 

@@ -154,6 +154,21 @@ def _read_kept(res, ids, num_nodes):
     return kept
 
 
+def _edge_operands(q, k, scale):
+    """Operands of the edge-attention entry points (include/difformer_edges.h): q [N,H,M], k [L,H,M] float32 as aligned rows
+    (views that are not are copied), scale [N,H] float32 dense or None -> (device, leading arguments, tensors to keep alive)."""
+    dev = _require_device(q, k, scale)
+    _all_f32(q=q, k=k, scale=scale)
+    N, H, M = q.shape
+    q, ldq = _rows(q, H * M, align=True)
+    k, ldk = _rows(k, H * M, align=True)
+    if scale is not None:
+        if tuple(scale.shape) != (N, H):
+            raise ValueError(f"difformer_amd: scale must be [N, H] = [{N}, {H}] (got {tuple(scale.shape)})")
+        scale = scale.contiguous()
+    return dev, (_ptr(q), ldq, _ptr(k), ldk, _ptr(scale), N, k.shape[0], H, M), (q, k, scale)
+
+
 class _Timed:
     """HIP-event bracket around one C-ABI call (events on the launching stream): the slow path of HipBackend._call."""
 
@@ -204,13 +219,14 @@ class HipBackend:
         torch.cuda.synchronize()
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
-    def _call(self, label, symbol, dev, *args, maps=False):
+    def _call(self, label, symbol, dev, *args, maps=False, edges=False):
         """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
         a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
         `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
-        collection, operands on the current device -- adds nothing around the call.  maps: `symbol` is one of
-        libdifformer_maps.so (include/difformer_maps.h), loaded on first use."""
-        fn = getattr(_lib.load_maps() if maps else self.lib, symbol)
+        collection, operands on the current device -- adds nothing around the call.  maps / edges: `symbol` is one of
+        libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so (include/difformer_edges.h), loaded on
+        first use."""
+        fn = getattr(_lib.load_maps() if maps else (_lib.load_edges() if edges else self.lib), symbol)
         index = dev.index
         if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
             rc = fn(*args, _raw_stream(index) if _raw_stream is not None else _stream(dev))
@@ -218,7 +234,7 @@ class HipBackend:
             with _Timed(self, label, dev):
                 rc = fn(*args, _stream(dev))
         if rc != 0:
-            (_lib.check_maps if maps else _lib.check)(rc, symbol)
+            (_lib.check_maps if maps else (_lib.check_edges if edges else _lib.check))(rc, symbol)
 
     # ---- a1 --------------------------------------------------------------------------------
     def simple_reduce(self, q, k, v):
@@ -368,6 +384,36 @@ class HipBackend:
         self._call("dif_attn_topk_f32", "dif_attn_topk_f32", dev, _ptr(q), ldq, _ptr(k), ldk, N, L, H, M, int(mode), int(topk),
                    _ptr(values), _ptr(indices), _ptr(ws), ws_bytes, maps=True)
         return values, indices
+
+    # ---- attention on graph edges (libdifformer_edges.so) ----------------------------------------
+    def edge_attention(self, q, k, scale, edge_index, mode):
+        """q [N,H,M], k [L,H,M] float32 (M a multiple of 4 up to 512), scale [N,H] float32 or None, edge_index int64 [2,E]
+        (row 0 the key id, row 1 the query id) -> (out float32 [E,H], status int32 [3]): out[e,h] = f(q[col_e,h] . k[row_e,h])
+        scale[col_e,h] with f the identity (mode 0) or sigma (mode 1).  An id out of range gives NaN for its edge and
+        status = [any, a key id, a query id] != 0; the caller reads it (csrc/attn_edges.hip)."""
+        dev, head, keep = _edge_operands(q, k, scale)
+        _require_device(q, edge_index)
+        _check_edge_index(edge_index)
+        ei = edge_index.contiguous()
+        E, H = int(ei.shape[1]), q.shape[1]
+        out = torch.empty((E, H), dtype=torch.float32, device=dev)
+        status = torch.empty(3, dtype=torch.int32, device=dev)
+        self._call("dif_edge_attn_f32", "dif_edge_attn_f32", dev, *head, int(mode), _ptr(ei), E, _ptr(out), _ptr(status), edges=True)
+        return out, status
+
+    def edge_attention_mass(self, q, k, scale, rowptr, src, mode):
+        """Operands as edge_attention; rowptr int32 [>= N + 1], src int32: the target-row CSR of csr_build -> mass float32
+        [N,H]: mass[n,h] = scale[n,h] sum_j f(q[n,h] . k[src[j],h]) over row n's entries, in an order that depends on M alone."""
+        dev, head, keep = _edge_operands(q, k, scale)
+        _require_device(q, rowptr, src)
+        N, H = q.shape[0], q.shape[1]
+        if rowptr.dtype != torch.int32 or src.dtype != torch.int32 or rowptr.numel() < N + 1:
+            raise TypeError("difformer_amd: rowptr (at least N + 1 entries) and src must be int32")
+        rowptr, src = rowptr.contiguous(), src.contiguous()
+        mass = torch.empty((N, H), dtype=torch.float32, device=dev)
+        self._call("dif_edge_attn_mass_f32", "dif_edge_attn_mass_f32", dev, *head, int(mode), _ptr(rowptr), _ptr(src), int(src.numel()),
+                   _ptr(mass), edges=True)
+        return mass
 
     def sigmoid_backward(self, q, k, v, out, den, g):
         """(dq, dk, dv) of the sigmoid kernel for fp32 q [N,H,M], k [L,H,M], v [L,H,D], out / g [N,H,D], den [N,H];

@@ -703,3 +703,45 @@ class DIFFormer(nn.Module):
                 x = ag.layer_tail(c, None, layer_[i] if self.residual else None, self.alpha, *_ln_args(bn))
                 layer_.append(x)
             return torch.stack(values, dim=0), torch.stack(indices, dim=0)
+
+    def edge_attentions(self, x, edge_index, mass=False):
+        """Per layer the attention ON THE EDGES of a graph: float32 [layers,E,H] with
+        `edge_attentions(x, ei)[l, e, h] == get_attentions(x)[l, ei[1, e], ei[0, e], h]` (row 0 of edge_index the source = key,
+        row 1 the target = query, as gcn_conv reads it), in the caller's edge order; mass=True: -> (that, float32 [layers,N,H]),
+        per node the sum over its in-edges -- the share of its attention row that lies on the graph.  One dot product per
+        edge (attention_maps.attention_on_edges): nothing of size N x N exists.  Same layers as get_attentions (no graph term
+        in the propagation, as in the reference); outputs are detached."""
+        from .attention_maps import _check_edges, attention_on_edges
+        if any(conv.row_shard is not None for conv in self.convs):
+            raise NotImplementedError("difformer_amd: edge_attentions of a row-sharded model is not implemented (a rank holds "
+                                      "the key rows of its own shard only)")
+        _check_edges(edge_index)
+        dev = staging.staging_device(self, (x, edge_index))
+        if dev is not None:      # model and operands in host memory: the device twin's result, returned on the host
+            twin = staging.twin_of(self, dev)
+            twin.refresh(self)
+            out = twin.module.edge_attentions(staging.operands.get(x, dev), staging.operands.get(edge_index, dev), mass)
+            return tuple(o.to(x.device) for o in out) if mass else out.to(x.device)
+        with torch.no_grad():
+            layer_, values, masses = [], [], []
+            csr = [None]                                       # one CSR of the edge list for all layers: built by the first
+            x = self._input_layer(x, False)
+            layer_.append(x)
+            for i, conv in enumerate(self.convs):
+                q, kk, v = conv._project(x, x)
+                v_att = v if v.shape[1] == conv.num_heads else v.expand(-1, conv.num_heads, -1).contiguous()
+                den = None
+                if conv.kernel == "sigmoid" and q.dtype == torch.float32:
+                    # ONE forward: its output is the layer's, its row sums the denominators of the map
+                    c, den = ops.get_backend().sigmoid_attention(q, kk, v_att, want_den=True)
+                else:
+                    c = full_attention_conv(q, kk, v_att, conv.kernel)
+                out = attention_on_edges(q, kk, conv.kernel, edge_index, mass, _den=den, _csr=csr)
+                values.append(out[0] if mass else out)
+                if mass:
+                    masses.append(out[1])
+                bn = self.bns[i + 1] if self.use_bn else None
+                x = ag.layer_tail(c, None, layer_[i] if self.residual else None, self.alpha, *_ln_args(bn))
+                layer_.append(x)
+            values = torch.stack(values, dim=0)
+            return (values, torch.stack(masses, dim=0)) if mass else values
