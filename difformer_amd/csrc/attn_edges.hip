@@ -44,6 +44,12 @@ int edges_fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
+// post-launch check into THIS library's error text (hipGetLastError only, never synchronises)
+int edges_launch_status(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return edges_fail(static_cast<int>(e), "%s: %s", what, hipGetErrorString(e));
+    return 0;
+}
 #define EDGES_REQUIRE(cond, code, ...) \
     do { if (!(cond)) return edges_fail((code), __VA_ARGS__); } while (0)
 
@@ -190,7 +196,7 @@ int check_operands(const char* who, const float* q, int64_t ldq, const float* k,
     EDGES_REQUIRE(n_q > 0 && n_k > 0 && H > 0 && M > 0, DIF_E_BADARG, "%s: n_q, n_k, H, M must be positive", who);
     EDGES_REQUIRE(q && k, DIF_E_BADARG, "%s: null pointer", who);
     EDGES_REQUIRE(dif::aligned16(q) && dif::aligned16(k), DIF_E_BADARG, "%s: q and k must be 16-byte aligned", who);
-    EDGES_REQUIRE((reinterpret_cast<uintptr_t>(scale) & 3u) == 0, DIF_E_BADARG, "%s: scale must be 4-byte aligned", who);
+    EDGES_REQUIRE(dif::aligned<4>(scale), DIF_E_BADARG, "%s: scale must be 4-byte aligned", who);
     EDGES_REQUIRE(M % 4 == 0 && M <= kMaxM, DIF_E_SHAPE, "%s: M must be a multiple of 4 up to %d (got %d); zero-pad the columns", who,
                   kMaxM, M);
     EDGES_REQUIRE(mode == 0 || mode == 1, DIF_E_SHAPE, "%s: unknown mode %d (0: simple, 1: sigmoid)", who, mode);
@@ -207,9 +213,7 @@ int launch_edges(const float* q, int64_t ldq, const float* k, int64_t ldk, const
     const dim3 grid(static_cast<unsigned>((E + per - 1) / per), static_cast<unsigned>(H));
     hipLaunchKernelGGL((edge_attn_kernel<G, MODE>), grid, dim3(kBlock), 0, st, q, ldq, k, ldk, scale, n_q, n_k, H, M, edge_index, E, out,
                        status);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return edges_fail(static_cast<int>(e), "edge_attn_kernel: %s", hipGetErrorString(e));
-    return 0;
+    return edges_launch_status("edge_attn_kernel");
 }
 
 template <int G, int MODE>
@@ -218,9 +222,7 @@ int launch_mass(const float* q, int64_t ldq, const float* k, int64_t ldk, const 
     const dim3 grid(static_cast<unsigned>((n_q + kBlock / 64 - 1) / (kBlock / 64)), static_cast<unsigned>(H));
     hipLaunchKernelGGL((edge_mass_kernel<G, MODE>), grid, dim3(kBlock), 0, st, q, ldq, k, ldk, scale, n_q, n_k, H, M, rowptr, src, nnz,
                        mass);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return edges_fail(static_cast<int>(e), "edge_mass_kernel: %s", hipGetErrorString(e));
-    return 0;
+    return edges_launch_status("edge_mass_kernel");
 }
 
 }  // namespace
@@ -228,21 +230,14 @@ int launch_mass(const float* q, int64_t ldq, const float* k, int64_t ldk, const 
 extern "C" int dif_edges_version(void) { return DIF_EDGES_VERSION; }
 extern "C" const char* dif_edges_last_error(void) { return edges_err_buf(); }
 
-// one launcher per (lane group, mode): G from M alone
-#define DIF_EDGES_DISPATCH(FN, ...)                                   \
-    do {                                                              \
-        const int G = group_lanes(M);                                 \
-        if (mode == 0) {                                              \
-            if (G == 4) return FN<4, 0>(__VA_ARGS__);                 \
-            if (G == 16) return FN<16, 0>(__VA_ARGS__);               \
-            if (G == 32) return FN<32, 0>(__VA_ARGS__);               \
-            return FN<64, 0>(__VA_ARGS__);                            \
-        }                                                             \
-        if (G == 4) return FN<4, 1>(__VA_ARGS__);                     \
-        if (G == 16) return FN<16, 1>(__VA_ARGS__);                   \
-        if (G == 32) return FN<32, 1>(__VA_ARGS__);                   \
-        return FN<64, 1>(__VA_ARGS__);                                \
-    } while (0)
+// one launcher per (lane group, mode): f(G, MODE) with both as constants, G from M alone
+template <typename F>
+static int with_group_and_mode(const char* who, int M, int mode, F&& f) {
+    auto miss = [who](int v) { return edges_fail(DIF_E_SHAPE, "%s: no kernel variant for %d", who, v); };
+    return dif::with_int<0, 1>(mode, [&](auto MODE) {
+        return dif::with_int<4, 16, 32, 64>(group_lanes(M), [&](auto G) { return f(G, MODE); }, miss);
+    }, miss);
+}
 
 extern "C" int dif_edge_attn_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* scale, int64_t n_q,
                                  int64_t n_k, int H, int M, int mode, const int64_t* edge_index, int64_t E, float* out,
@@ -250,14 +245,16 @@ extern "C" int dif_edge_attn_f32(const float* q, int64_t ldq, const float* k, in
     const char* who = "dif_edge_attn_f32";
     if (const int rc = check_operands(who, q, ldq, k, ldk, scale, n_q, n_k, H, M, mode)) return rc;
     EDGES_REQUIRE(edge_index && out && status, DIF_E_BADARG, "%s: null pointer", who);
-    EDGES_REQUIRE((reinterpret_cast<uintptr_t>(edge_index) & 7u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 &&
-                      (reinterpret_cast<uintptr_t>(status) & 3u) == 0,
+    EDGES_REQUIRE(dif::aligned<8>(edge_index) && dif::aligned<4>(out) &&
+                      dif::aligned<4>(status),
                   DIF_E_BADARG, "%s: edge_index must be 8-byte aligned, out and status 4-byte aligned", who);
     EDGES_REQUIRE(E >= 1 && E < (1ll << 31), DIF_E_RANGE, "%s: E must be in [1, 2^31) (got %lld)", who, static_cast<long long>(E));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const hipError_t e = hipMemsetAsync(status, 0, 3 * sizeof(int32_t), st);
     if (e != hipSuccess) return edges_fail(static_cast<int>(e), "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
-    DIF_EDGES_DISPATCH(launch_edges, q, ldq, k, ldk, scale, n_q, n_k, H, M, edge_index, E, out, status, st);
+    return with_group_and_mode(who, M, mode, [&](auto G, auto MODE) {
+        return launch_edges<G, MODE>(q, ldq, k, ldk, scale, n_q, n_k, H, M, edge_index, E, out, status, st);
+    });
 }
 
 extern "C" int dif_edge_attn_mass_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* scale, int64_t n_q,
@@ -266,12 +263,13 @@ extern "C" int dif_edge_attn_mass_f32(const float* q, int64_t ldq, const float* 
     const char* who = "dif_edge_attn_mass_f32";
     if (const int rc = check_operands(who, q, ldq, k, ldk, scale, n_q, n_k, H, M, mode)) return rc;
     EDGES_REQUIRE(rowptr && src && mass, DIF_E_BADARG, "%s: null pointer", who);
-    EDGES_REQUIRE((reinterpret_cast<uintptr_t>(rowptr) & 3u) == 0 && (reinterpret_cast<uintptr_t>(src) & 3u) == 0 &&
-                      (reinterpret_cast<uintptr_t>(mass) & 3u) == 0,
+    EDGES_REQUIRE(dif::aligned<4>(rowptr) && dif::aligned<4>(src) &&
+                      dif::aligned<4>(mass),
                   DIF_E_BADARG, "%s: rowptr, src and mass must be 4-byte aligned", who);
     EDGES_REQUIRE(nnz >= 0 && nnz < (1ll << 31), DIF_E_RANGE, "%s: nnz must be in [0, 2^31) (got %lld)", who, static_cast<long long>(nnz));
     EDGES_REQUIRE((n_q + 3) / 4 < (1ll << 31), DIF_E_RANGE, "%s: grid too large", who);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    DIF_EDGES_DISPATCH(launch_mass, q, ldq, k, ldk, scale, n_q, n_k, H, M, rowptr, src, nnz, mass, st);
+    return with_group_and_mode(who, M, mode, [&](auto G, auto MODE) {
+        return launch_mass<G, MODE>(q, ldq, k, ldk, scale, n_q, n_k, H, M, rowptr, src, nnz, mass, st);
+    });
 }
-#undef DIF_EDGES_DISPATCH

@@ -53,6 +53,12 @@ int maps_fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
+// post-launch check into THIS library's error text (hipGetLastError only, never synchronises)
+int maps_launch_status(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return maps_fail(static_cast<int>(e), "%s: %s", what, hipGetErrorString(e));
+    return 0;
+}
 #define MAPS_REQUIRE(cond, code, ...) \
     do { if (!(cond)) return maps_fail((code), __VA_ARGS__); } while (0)
 
@@ -304,18 +310,14 @@ template <int KMAX, int MODE>
 int launch(const float* q, int64_t ldq, const float* k, int64_t ldk, int64_t N, int64_t L, int H, int M, int topk, int S,
            float* values, int32_t* indices, uint64_t* lists, float* psum, hipStream_t st) {
     const dim3 grid(static_cast<unsigned>((N + kQGroup - 1) / kQGroup), static_cast<unsigned>(H), static_cast<unsigned>(S));
-    if (M <= 64)
-        hipLaunchKernelGGL((attn_topk_sweep_kernel<KMAX, MODE, true>), grid, dim3(64), 0, st, q, ldq, k, ldk, N, L, H, M, lists, psum);
-    else
-        hipLaunchKernelGGL((attn_topk_sweep_kernel<KMAX, MODE, false>), grid, dim3(64), 0, st, q, ldq, k, ldk, N, L, H, M, lists, psum);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return maps_fail(static_cast<int>(e), "attn_topk_sweep_kernel: %s", hipGetErrorString(e));
+    if (int rc = dif::with_flags([&](auto QREG) {              // heads of up to 64 columns: the query fragments stay in registers
+            hipLaunchKernelGGL((attn_topk_sweep_kernel<KMAX, MODE, QREG>), grid, dim3(64), 0, st, q, ldq, k, ldk, N, L, H, M, lists, psum);
+            return maps_launch_status("attn_topk_sweep_kernel");
+        }, M <= 64)) return rc;
     const int64_t rows = N * H;
     hipLaunchKernelGGL((attn_topk_merge_kernel<KMAX, MODE>), dim3(static_cast<unsigned>((rows + 255) / 256)), dim3(256), 0, st,
                        lists, psum, rows, S, topk, values, indices);
-    e = hipGetLastError();
-    if (e != hipSuccess) return maps_fail(static_cast<int>(e), "attn_topk_merge_kernel: %s", hipGetErrorString(e));
-    return 0;
+    return maps_launch_status("attn_topk_merge_kernel");
 }
 
 }  // namespace
@@ -343,7 +345,7 @@ extern "C" int dif_attn_topk_f32(const float* q, int64_t ldq, const float* k, in
     MAPS_REQUIRE(q && k && values && indices && workspace, DIF_E_BADARG, "%s: null pointer", who);
     MAPS_REQUIRE(dif::aligned16(q) && dif::aligned16(k) && dif::aligned16(workspace), DIF_E_BADARG,
                  "%s: q, k and the workspace must be 16-byte aligned", who);
-    MAPS_REQUIRE((reinterpret_cast<uintptr_t>(values) & 3u) == 0 && (reinterpret_cast<uintptr_t>(indices) & 3u) == 0, DIF_E_BADARG,
+    MAPS_REQUIRE(dif::aligned<4>(values) && dif::aligned<4>(indices), DIF_E_BADARG,
                  "%s: values and indices must be 4-byte aligned", who);
     MAPS_REQUIRE(M % 4 == 0 && M <= kMaxM, DIF_E_SHAPE, "%s: M must be a multiple of 4 up to %d (got %d); zero-pad the columns", who,
                  kMaxM, M);
@@ -363,15 +365,10 @@ extern "C" int dif_attn_topk_f32(const float* q, int64_t ldq, const float* k, in
     uint64_t* lists = static_cast<uint64_t*>(workspace);
     float* psum = reinterpret_cast<float*>(lists + static_cast<int64_t>(S) * n_q * H * KM);
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define DIF_TOPK_LAUNCH(KX, MD) \
-    return launch<KX, MD>(q, ldq, k, ldk, n_q, n_k, H, M, topk, S, values, indices, lists, psum, st)
-    if (mode == 0) {
-        if (KM == 8) DIF_TOPK_LAUNCH(8, 0);
-        if (KM == 16) DIF_TOPK_LAUNCH(16, 0);
-        DIF_TOPK_LAUNCH(32, 0);
-    }
-    if (KM == 8) DIF_TOPK_LAUNCH(8, 1);
-    if (KM == 16) DIF_TOPK_LAUNCH(16, 1);
-    DIF_TOPK_LAUNCH(32, 1);
-#undef DIF_TOPK_LAUNCH
+    auto miss = [who](int v) { return maps_fail(DIF_E_SHAPE, "%s: no kernel variant for %d", who, v); };
+    return dif::with_int<0, 1>(mode, [&](auto MODE) {
+        return dif::with_int<8, 16, 32>(KM, [&](auto KMAX) {
+            return launch<KMAX, MODE>(q, ldq, k, ldk, n_q, n_k, H, M, topk, S, values, indices, lists, psum, st);
+        }, miss);
+    }, miss);
 }

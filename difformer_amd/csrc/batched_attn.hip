@@ -272,20 +272,13 @@ int launch_batched(hipStream_t st, const float* q, int64_t ldq, const float* k, 
     const bool vec = (M % 4 == 0) && (D % 4 == 0) && (ldq % 4 == 0) && (ldk % 4 == 0) && (ldv % 4 == 0) && (ldo % 4 == 0) &&
                      dif::aligned16(q) && dif::aligned16(k) && dif::aligned16(v) && dif::aligned16(out);
     const int MT = (M + 63) / 64;
-#define DIF_LAUNCH_BS2(MTV, V, W, R) \
-    hipLaunchKernelGGL((batched_simple_kernel<MTV, V, W, R>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, st, q, ldq, k, ldk, \
-                       v, ldv, graph_ptr, n_graphs, H, M, D, sumsq, out, ldo, ex)
-#define DIF_LAUNCH_BS(MTV, V) \
-    do { \
-        if (wide) { if (raw) DIF_LAUNCH_BS2(MTV, V, 4, true); else DIF_LAUNCH_BS2(MTV, V, 4, false); } \
-        else { if (raw) DIF_LAUNCH_BS2(MTV, V, 1, true); else DIF_LAUNCH_BS2(MTV, V, 1, false); } \
-    } while (0)
-    if (MT == 1) { if (vec) DIF_LAUNCH_BS(1, true); else DIF_LAUNCH_BS(1, false); }
-    else if (MT == 2) { if (vec) DIF_LAUNCH_BS(2, true); else DIF_LAUNCH_BS(2, false); }
-    else { if (vec) DIF_LAUNCH_BS(4, true); else DIF_LAUNCH_BS(4, false); }
-#undef DIF_LAUNCH_BS
-#undef DIF_LAUNCH_BS2
-    return dif::launch_status("batched_simple_kernel");
+    const int mtv = MT >= 3 ? 4 : MT;                          // 3 and 4 column tiles share the 4-tile kernel
+    return dif::with_int<1, 2, 4>(mtv, [&](auto MTV) {
+        return dif::with_flags([&](auto VEC, auto WIDE, auto RAW) {
+            return dif::launch("batched_simple_kernel", batched_simple_kernel<MTV, VEC, WIDE ? 4 : 1, RAW>, dif::grid_of(grid),
+                               dim3(256), 0, st, q, ldq, k, ldk, v, ldv, graph_ptr, n_graphs, H, M, D, sumsq, out, ldo, ex);
+        }, vec, wide, raw);
+    }, dif::no_variant("batched_simple_kernel"));
 }
 
 int batched_forward(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
@@ -310,10 +303,10 @@ int batched_forward(const float* q, int64_t ldq, const float* k, int64_t ldk, co
     int64_t ng = (n_rows * ((static_cast<int64_t>(H) * M + 3) / 4) + 1023) / 1024;     // >= 4 float4 per thread
     if (ng > kNormWG) ng = kNormWG;
     if (ng < 1) ng = 1;
-    hipLaunchKernelGGL(sumsq_pair_kernel, dim3(static_cast<unsigned>(ng)), dim3(256), 0, st, q, ldq, k, ldk, n_rows, H * M, part);
-    if (int rc = dif::launch_status("sumsq_pair_kernel")) return rc;
-    hipLaunchKernelGGL(sumsq_fold_kernel, dim3(1), dim3(64), 0, st, part, static_cast<int>(ng), sumsq);
-    if (int rc = dif::launch_status("sumsq_fold_kernel")) return rc;
+    if (int rc = dif::launch("sumsq_pair_kernel", sumsq_pair_kernel, dif::grid_of(ng), dim3(256), 0, st, q, ldq, k, ldk, n_rows,
+                             H * M, part)) return rc;
+    if (int rc = dif::launch("sumsq_fold_kernel", sumsq_fold_kernel, dim3(1), dim3(64), 0, st, part, static_cast<int>(ng),
+                             sumsq)) return rc;
     const BatchedExtra ex = {nullptr, nullptr, 0, den};
     return launch_batched(st, q, ldq, k, ldk, v, ldv, graph_ptr, n_graphs, n_rows, H, M, D, sumsq, out, ldo, false, ex);
 }

@@ -11,7 +11,13 @@ namespace dif {
 char* err_buf();
 int fail(int code, const char* fmt, ...);
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// p is a multiple of N bytes (N a power of two)
+template <int N>
+__host__ __device__ __forceinline__ bool aligned(const void* p) {
+    static_assert(N > 0 && (N & (N - 1)) == 0, "dif::aligned: N must be a power of two");
+    return (reinterpret_cast<uintptr_t>(p) & static_cast<uintptr_t>(N - 1)) == 0;
+}
+inline bool aligned16(const void* p) { return aligned<16>(p); }
 
 // Post-launch check: hipGetLastError only (never synchronises).
 int launch_status(const char* what);
@@ -233,3 +239,5 @@ __device__ __forceinline__ f32x4 mask4(f32x4 z, bool rok, int c, int width) {
 }
 
 }  // namespace dif
+
+#include "dif_launch.h"

@@ -157,11 +157,10 @@ __global__ __launch_bounds__(kScanBlock) void scan_apply_kernel(const int32_t* i
 int exclusive_scan(const int32_t* in, int64_t n, int32_t* out, int32_t* out_total, int32_t* bsum,
                    hipStream_t st) {
     const int64_t nb = (n + kScanTile - 1) / kScanTile;
-    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanBlock), 0, st, in, n, bsum);
-    hipLaunchKernelGGL(scan_of_sums_kernel, dim3(1), dim3(1024), 0, st, bsum, nb);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanBlock), 0, st, in, n, bsum, nb,
-                       out, out_total);
-    return dif::launch_status("exclusive_scan");
+    if (int rc = dif::launch("exclusive_scan", scan_block_sums_kernel, dif::grid_of(nb), dim3(kScanBlock), 0, st, in, n, bsum)) return rc;
+    if (int rc = dif::launch("exclusive_scan", scan_of_sums_kernel, dim3(1), dim3(1024), 0, st, bsum, nb)) return rc;
+    return dif::launch("exclusive_scan", scan_apply_kernel, dif::grid_of(nb), dim3(kScanBlock), 0, st, in, n, bsum, nb, out,
+                       out_total);
 }
 
 // From the key pointers kptr[dst*NB + blk]: rowptr, block-major blkptr, and
@@ -695,13 +694,11 @@ int radix_sort(const SortGeom& g, SortBufs& b, hipStream_t st) {
     const unsigned sort_grid = static_cast<unsigned>((g.n_chunks + kSortWaves - 1) / kSortWaves);
     for (int pass = 0; pass < g.passes; ++pass) {
         const int shift = pass * kRadixBits;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin, g.n, shift, g.n_chunks,
-                           g.rounds, b.table);
-        if (int rc = dif::launch_status("radix_hist_kernel")) return rc;
+        if (int rc = dif::launch("radix_hist_kernel", radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin, g.n,
+                                 shift, g.n_chunks, g.rounds, b.table)) return rc;
         if (int rc = exclusive_scan(b.table, g.table_len, b.table, nullptr, b.bsum, st)) return rc;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin, b.vin, g.n, shift,
-                           g.n_chunks, g.rounds, b.table, b.kout, b.vout);
-        if (int rc = dif::launch_status("radix_scatter_kernel")) return rc;
+        if (int rc = dif::launch("radix_scatter_kernel", radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin,
+                                 b.vin, g.n, shift, g.n_chunks, g.rounds, b.table, b.kout, b.vout)) return rc;
         uint32_t* t = b.kin; b.kin = b.kout; b.kout = t;
         t = b.vin; b.vin = b.vout; b.vout = t;
     }
@@ -876,24 +873,20 @@ extern "C" int dif_csr_build(const int64_t* edge_index, int64_t E, int64_t N, co
 
     if (E == 0) {           // no entries: every pointer is 0
         if (int rc = zero_async("dif_csr_build", kcnt, static_cast<size_t>(p.n_keys + 1) * 4, st)) return rc;
-        hipLaunchKernelGGL(csr_ptrs_kernel, dim3(static_cast<unsigned>((N + 256) / 256)), dim3(256), 0, st, kcnt, N, p.NB,
+        return dif::launch("csr_ptrs_kernel", csr_ptrs_kernel, dif::grid_of((N + 256) / 256), dim3(256), 0, st, kcnt, N, p.NB,
                            rowptr, n_blocks > 1 ? blkptr : nullptr, degc, dinv, status + 1);
-        return dif::launch_status("csr_ptrs_kernel");
     }
-    hipLaunchKernelGGL(csr_count_kernel, dim3(capped_grid(E)), dim3(256), 0, st, edge_index, E, N, p.NB, p.block_rows,
-                       transpose, edge_weight != nullptr, b.kin, b.vin, degc, status);
-    if (int rc = dif::launch_status("csr_count_kernel")) return rc;
+    if (int rc = dif::launch("csr_count_kernel", csr_count_kernel, dim3(capped_grid(E)), dim3(256), 0, st, edge_index, E, N, p.NB,
+                             p.block_rows, transpose, edge_weight != nullptr, b.kin, b.vin, degc, status)) return rc;
     if (int rc = radix_sort(p.sort, b, st)) return rc;
     const unsigned g = capped_grid(E + 1);
     // key pointers kptr[0 .. N*NB] from the sorted keys, then rowptr / blkptr / dinv
-    hipLaunchKernelGGL(csr_bounds_kernel, dim3(g), dim3(256), 0, st, b.kin, E, p.n_keys, kcnt);
-    if (int rc = dif::launch_status("csr_bounds_kernel")) return rc;
-    hipLaunchKernelGGL(csr_ptrs_kernel, dim3(static_cast<unsigned>((N + 256) / 256)), dim3(256), 0, st, kcnt, N, p.NB,
-                       rowptr, n_blocks > 1 ? blkptr : nullptr, degc, dinv, status + 1);
-    if (int rc = dif::launch_status("csr_ptrs_kernel")) return rc;
-    hipLaunchKernelGGL(csr_fill_kernel, dim3(g), dim3(256), 0, st, edge_index, E, N, static_cast<uint32_t>(p.NB), transpose,
-                       edge_weight, b.kin, b.vin, dinv, src, val);
-    return dif::launch_status("csr_fill_kernel");
+    if (int rc = dif::launch("csr_bounds_kernel", csr_bounds_kernel, dim3(g), dim3(256), 0, st, b.kin, E, p.n_keys,
+                             kcnt)) return rc;
+    if (int rc = dif::launch("csr_ptrs_kernel", csr_ptrs_kernel, dif::grid_of((N + 256) / 256), dim3(256), 0, st, kcnt, N, p.NB,
+                             rowptr, n_blocks > 1 ? blkptr : nullptr, degc, dinv, status + 1)) return rc;
+    return dif::launch("csr_fill_kernel", csr_fill_kernel, dim3(g), dim3(256), 0, st, edge_index, E, N, static_cast<uint32_t>(p.NB),
+                       transpose, edge_weight, b.kin, b.vin, dinv, src, val);
 }
 
 extern "C" size_t dif_row_order_workspace_bytes(int64_t n_rows) {
@@ -918,9 +911,8 @@ extern "C" int dif_row_order(const int32_t* rowptr, int64_t row_begin, int64_t n
     SortBufs b{at<uint32_t>(ws, p.off_ka), at<uint32_t>(ws, p.off_kb), at<uint32_t>(ws, p.off_va), reinterpret_cast<uint32_t*>(order),
                at<int32_t>(ws, p.off_table), at<int32_t>(ws, p.off_bsum)};
     if (int rc = zero_async("dif_row_order", stats, 8, st)) return rc;
-    hipLaunchKernelGGL(order_keys_kernel, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0, st, rowptr,
-                       row_begin, n_rows, b.kin, b.vin, stats);
-    if (int rc = dif::launch_status("order_keys_kernel")) return rc;
+    if (int rc = dif::launch("order_keys_kernel", order_keys_kernel, dif::grid_of((n_rows + 255) / 256), dim3(256), 0, st, rowptr,
+                             row_begin, n_rows, b.kin, b.vin, stats)) return rc;
     return radix_sort(p.sort, b, st);
 }
 
@@ -952,17 +944,14 @@ extern "C" int dif_subgraph(const int64_t* edge_index, int64_t E, int64_t N, con
     if (int rc = zero_async("dif_subgraph", member, static_cast<size_t>((N + 31) / 32) * 4, st)) return rc;
     if (int rc = zero_async("dif_subgraph", status, 4, st)) return rc;
     if (B > 0) {
-        hipLaunchKernelGGL(subgraph_mark_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, st, subset, B,
-                           N, newid, member, status);
-        if (int rc = dif::launch_status("subgraph_mark_kernel")) return rc;
+        if (int rc = dif::launch("subgraph_mark_kernel", subgraph_mark_kernel, dif::grid_of((B + 255) / 256), dim3(256), 0, st,
+                                 subset, B, N, newid, member, status)) return rc;
     }
-    hipLaunchKernelGGL(subgraph_mask_kernel, dim3(capped_blocks(p.n_chunks + 1)), dim3(256), 0, st, edge_index, E, N, member,
-                       mask, counts, p.n_chunks, status);
-    if (int rc = dif::launch_status("subgraph_mask_kernel")) return rc;
+    if (int rc = dif::launch("subgraph_mask_kernel", subgraph_mask_kernel, dim3(capped_blocks(p.n_chunks + 1)), dim3(256), 0, st,
+                             edge_index, E, N, member, mask, counts, p.n_chunks, status)) return rc;
     if (int rc = exclusive_scan(counts, p.n_chunks + 1, counts, nullptr, bsum, st)) return rc;
-    hipLaunchKernelGGL(subgraph_compact_kernel, dim3(capped_blocks((p.n_chunks + 3) / 4)), dim3(256), 0, st, edge_index, E,
-                       edge_weight, newid, mask, counts, p.n_chunks, E, out_edge_index, out_weight, out_count);
-    return dif::launch_status("subgraph_compact_kernel");
+    return dif::launch("subgraph_compact_kernel", subgraph_compact_kernel, dim3(capped_blocks((p.n_chunks + 3) / 4)), dim3(256), 0,
+                       st, edge_index, E, edge_weight, newid, mask, counts, p.n_chunks, E, out_edge_index, out_weight, out_count);
 }
 
 extern "C" size_t dif_subgraph_batches_workspace_bytes(int64_t E, int64_t N, int n_batches) {
@@ -989,16 +978,14 @@ extern "C" int dif_subgraph_batches_group(const int64_t* edge_index, int64_t E, 
     SortBufs b = sort_bufs(ws, p);
     if (int rc = zero_async("dif_subgraph_batches", info, static_cast<size_t>(N) * 4, st)) return rc;
     if (int rc = zero_async("dif_subgraph_batches", status, 4, st)) return rc;
-    hipLaunchKernelGGL(batches_mark_kernel, dim3(static_cast<unsigned>((M + 255) / 256)), dim3(256), 0, st, perm, M, N, info, status);
-    if (int rc = dif::launch_status("batches_mark_kernel")) return rc;
+    if (int rc = dif::launch("batches_mark_kernel", batches_mark_kernel, dif::grid_of((M + 255) / 256), dim3(256), 0, st, perm, M,
+                             N, info, status)) return rc;
     if (E == 0) return zero_async("dif_subgraph_batches", batch_ptr, static_cast<size_t>(n_batches + 1) * 8, st);
     const unsigned g = capped_grid(E + 1);
-    hipLaunchKernelGGL(batches_key_kernel, dim3(g), dim3(256), 0, st, edge_index, E, N, info, static_cast<int32_t>(batch_size),
-                       p.sort.passes > 1 ? 1 : 0, b.kin, b.vin, status);
-    if (int rc = dif::launch_status("batches_key_kernel")) return rc;
+    if (int rc = dif::launch("batches_key_kernel", batches_key_kernel, dim3(g), dim3(256), 0, st, edge_index, E, N, info,
+                             static_cast<int32_t>(batch_size), p.sort.passes > 1 ? 1 : 0, b.kin, b.vin, status)) return rc;
     if (int rc = radix_sort(p.sort, b, st)) return rc;      // the ids end up at p.off_grouped()
-    hipLaunchKernelGGL(batches_ptr_kernel, dim3(g), dim3(256), 0, st, b.kin, E, n_batches, batch_ptr);
-    return dif::launch_status("batches_ptr_kernel");
+    return dif::launch("batches_ptr_kernel", batches_ptr_kernel, dim3(g), dim3(256), 0, st, b.kin, E, n_batches, batch_ptr);
 }
 
 // Phase 2: out_edge_index int64 [2, capacity] (row r at offset r * capacity), capacity >= batch_ptr[n_batches]:
@@ -1017,10 +1004,10 @@ extern "C" int dif_subgraph_batches_emit(const int64_t* edge_index, int64_t E, i
     DIF_REQUIRE(workspace_bytes >= p.total, DIF_E_WORKSPACE, "dif_subgraph_batches_emit: workspace too small");
     if (capacity == 0 || E == 0) return 0;
     const char* ws = static_cast<const char*>(workspace);
-    hipLaunchKernelGGL(batches_emit_kernel, dim3(capped_grid(capacity)), dim3(256), 0, static_cast<hipStream_t>(stream), edge_index,
-                       E, edge_weight, at<int32_t>(ws, p.off_info), static_cast<int32_t>(batch_size),
-                       at<uint32_t>(ws, p.off_grouped()), batch_ptr, n_batches, capacity, out_edge_index, out_weight);
-    return dif::launch_status("batches_emit_kernel");
+    return dif::launch("batches_emit_kernel", batches_emit_kernel, dim3(capped_grid(capacity)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), edge_index, E, edge_weight, at<int32_t>(ws, p.off_info),
+                       static_cast<int32_t>(batch_size), at<uint32_t>(ws, p.off_grouped()), batch_ptr, n_batches, capacity,
+                       out_edge_index, out_weight);
 }
 
 extern "C" size_t dif_subgraph_batches_csr_workspace_bytes(int64_t kept, int64_t M) {
@@ -1056,16 +1043,14 @@ extern "C" int dif_subgraph_batches_csr(const int64_t* edge_index, int64_t E, in
     float* dinv = at<float>(ws, p.off_dinv);
     if (kept == 0) return zero_async("dif_subgraph_batches_csr", rowptr, static_cast<size_t>(M + 1) * 4, st);
     const unsigned g = capped_grid(kept + 1);
-    hipLaunchKernelGGL(batches_csr_key_kernel, dim3(g), dim3(256), 0, st, edge_index, E, info, grouped, kept, b.kin, b.vin);
-    if (int rc = dif::launch_status("batches_csr_key_kernel")) return rc;
+    if (int rc = dif::launch("batches_csr_key_kernel", batches_csr_key_kernel, dim3(g), dim3(256), 0, st, edge_index, E, info,
+                             grouped, kept, b.kin, b.vin)) return rc;
     if (int rc = radix_sort(p.sort, b, st)) return rc;
-    hipLaunchKernelGGL(csr_bounds_kernel, dim3(g), dim3(256), 0, st, b.kin, kept, M, rowptr);
-    if (int rc = dif::launch_status("csr_bounds_kernel")) return rc;
-    hipLaunchKernelGGL(batches_csr_dinv_kernel, dim3(static_cast<unsigned>((M + 255) / 256)), dim3(256), 0, st, rowptr, M, dinv);
-    if (int rc = dif::launch_status("batches_csr_dinv_kernel")) return rc;
-    hipLaunchKernelGGL(batches_csr_fill_kernel, dim3(g), dim3(256), 0, st, edge_index, E, edge_weight, info,
-                       static_cast<int32_t>(batch_size), b.kin, b.vin, kept, dinv, src, val);
-    return dif::launch_status("batches_csr_fill_kernel");
+    if (int rc = dif::launch("csr_bounds_kernel", csr_bounds_kernel, dim3(g), dim3(256), 0, st, b.kin, kept, M, rowptr)) return rc;
+    if (int rc = dif::launch("batches_csr_dinv_kernel", batches_csr_dinv_kernel, dif::grid_of((M + 255) / 256), dim3(256), 0, st,
+                             rowptr, M, dinv)) return rc;
+    return dif::launch("batches_csr_fill_kernel", batches_csr_fill_kernel, dim3(g), dim3(256), 0, st, edge_index, E, edge_weight,
+                       info, static_cast<int32_t>(batch_size), b.kin, b.vin, kept, dinv, src, val);
 }
 
 extern "C" size_t dif_graph_prepare_workspace_bytes(int64_t E, int64_t N, int undirected) {
@@ -1095,22 +1080,20 @@ extern "C" int dif_graph_prepare(const int64_t* edge_index, int64_t E, int64_t N
     const unsigned g = capped_grid(n + 1);
     uint32_t *row = b.vin, *col = b.kin;           // after prep_pairs: key = col, payload = row
     if (E > 0) {
-        hipLaunchKernelGGL(prep_pairs_kernel, dim3(g), dim3(256), 0, st, edge_index, E, N, undirected, b.kin, b.vin, status);
-        if (int rc = dif::launch_status("prep_pairs_kernel")) return rc;
+        if (int rc = dif::launch("prep_pairs_kernel", prep_pairs_kernel, dim3(g), dim3(256), 0, st, edge_index, E, N, undirected,
+                                 b.kin, b.vin, status)) return rc;
     }
     if (undirected && n > 0) {
         // by col, then (stable) by row -> (row, col) order; in between keys <- rows, payload <- cols
         if (int rc = radix_sort(p.sort, b, st)) return rc;
-        hipLaunchKernelGGL(prep_swap_kernel, dim3(g), dim3(256), 0, st, b.kin, b.vin, n);
-        if (int rc = dif::launch_status("prep_swap_kernel")) return rc;
+        if (int rc = dif::launch("prep_swap_kernel", prep_swap_kernel, dim3(g), dim3(256), 0, st, b.kin, b.vin, n)) return rc;
         if (int rc = radix_sort(p.sort, b, st)) return rc;
         row = b.kin;
         col = b.vin;
     }
-    hipLaunchKernelGGL(prep_flag_kernel, dim3(g), dim3(256), 0, st, row, col, n, undirected, remove_loops, keep);
-    if (int rc = dif::launch_status("prep_flag_kernel")) return rc;
+    if (int rc = dif::launch("prep_flag_kernel", prep_flag_kernel, dim3(g), dim3(256), 0, st, row, col, n, undirected, remove_loops,
+                             keep)) return rc;
     if (int rc = exclusive_scan(keep, n + 1, keep, nullptr, b.bsum, st)) return rc;
-    hipLaunchKernelGGL(prep_emit_kernel, dim3(capped_grid(n > N ? n : N)), dim3(256), 0, st, row, col, n, keep, N, add_loops,
-                       capacity, out_edge_index, out_count);
-    return dif::launch_status("prep_emit_kernel");
+    return dif::launch("prep_emit_kernel", prep_emit_kernel, dim3(capped_grid(n > N ? n : N)), dim3(256), 0, st, row, col, n, keep,
+                       N, add_loops, capacity, out_edge_index, out_count);
 }

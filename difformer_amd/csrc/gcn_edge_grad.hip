@@ -64,11 +64,8 @@ extern "C" int dif_gcn_edge_weight_grad_f32(const int64_t* edge_index, int64_t E
     const int64_t want = (E + 15) / 16;                           // 16 edges per 256-thread workgroup and sweep
     const int grid = static_cast<int>(want < 8LL * dif::kCUs ? want : 8LL * dif::kCUs);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (vec)
-        hipLaunchKernelGGL(edge_weight_grad_kernel<4>, dim3(grid), dim3(256), 0, st, edge_index, E, edge_weight, rowptr, g, ldg,
-                           x, ldx, F, scale, dw);
-    else
-        hipLaunchKernelGGL(edge_weight_grad_kernel<1>, dim3(grid), dim3(256), 0, st, edge_index, E, edge_weight, rowptr, g, ldg,
-                           x, ldx, F, scale, dw);
-    return dif::launch_status("dif_gcn_edge_weight_grad_f32");
+    return dif::with_flags([&](auto VEC) {
+        return dif::launch("dif_gcn_edge_weight_grad_f32", edge_weight_grad_kernel<VEC ? 4 : 1>, dim3(grid), dim3(256), 0, st,
+                           edge_index, E, edge_weight, rowptr, g, ldg, x, ldx, F, scale, dw);
+    }, vec);
 }

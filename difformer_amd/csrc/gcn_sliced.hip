@@ -36,7 +36,8 @@ namespace {
 using dif::f32x4;
 using dif::dinv_of;
 
-// Geometry knobs of measurement builds (profiles/r03_experiments.md): the default is one 16-wave workgroup per CU with the
+// Geometry knobs of measurement builds (profiles/r03_experiments.md).  They stay macros: scripts/exp_sliced_variant.py rebuilds
+// this file with other values through the Makefile's EXTRA.  The default is one 16-wave workgroup per CU with the
 // whole LDS; -DDIF_SLICED_TILE_ROWS=5104 -DDIF_SLICED_MAX_WAVES=8 -DDIF_SLICED_WG_PER_CU=2 builds two 8-wave workgroups
 // per CU with 80 KiB each (one drains / loads its tile while the other computes; half-length lists).
 #ifndef DIF_SLICED_TILE_ROWS
@@ -865,13 +866,11 @@ __global__ __launch_bounds__(256) void sliced_combine_kernel(Plan pl, Epilogue e
 template <int R>
 int launch_sweep(hipStream_t st, const uint4* ell, const int32_t* tab, const f32x4* ys, int64_t npad, const Plan& pl,
                  const Epilogue& ep) {
-    hipLaunchKernelGGL((sliced_spmm_kernel<R>), dim3(static_cast<unsigned>(pl.panels * pl.S * pl.slices)), dim3(64 * pl.W),
-                       0, st, ell, tab, ys, npad, pl, ep);
-    if (int rc = dif::launch_status("sliced_spmm_kernel")) return rc;
+    if (int rc = dif::launch("sliced_spmm_kernel", sliced_spmm_kernel<R>, dif::grid_of(pl.panels * pl.S * pl.slices),
+                             dim3(64 * pl.W), 0, st, ell, tab, ys, npad, pl, ep)) return rc;
     if (pl.S == 1) return 0;
     const int64_t pairs = static_cast<int64_t>(pl.G) * pl.slices;            // one wave per (slot, slice)
-    hipLaunchKernelGGL(sliced_combine_kernel, dim3(static_cast<unsigned>((pairs + 3) / 4)), dim3(256), 0, st, pl, ep);
-    return dif::launch_status("sliced_combine_kernel");
+    return dif::launch("sliced_combine_kernel", sliced_combine_kernel, dif::grid_of((pairs + 3) / 4), dim3(256), 0, st, pl, ep);
 }
 
 // n_pos row positions: the n_rows rows themselves, or (parts != NULL) their parts plus padding
@@ -938,17 +937,14 @@ extern "C" int dif_sliced_measure(const int32_t* rowptr, const int32_t* blkptr, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t he = hipMemsetAsync(status, 0, 4, st);
     if (he != hipSuccess) return dif::fail(static_cast<int>(he), "dif_sliced_measure: memset: %s", hipGetErrorString(he));
-    hipLaunchKernelGGL(sliced_sort_kernel, dim3(static_cast<unsigned>((n_pos + 3) / 4)), dim3(256), 0, st, rowptr,
-                       blkptr, src, n_src, pl.NT, pl.T, row_begin, n_pos, row_order, parts, sorted,
-                       static_cast<uint4*>(counts), status);
-    if (int rc = dif::launch_status("sliced_sort_kernel")) return rc;
+    if (int rc = dif::launch("sliced_sort_kernel", sliced_sort_kernel, dif::grid_of((n_pos + 3) / 4), dim3(256), 0, st, rowptr,
+                             blkptr, src, n_src, pl.NT, pl.T, row_begin, n_pos, row_order, parts, sorted,
+                             static_cast<uint4*>(counts), status)) return rc;
     const int64_t n_hw = static_cast<int64_t>(pl.G) * pl.NT * 4;
-    hipLaunchKernelGGL((sliced_color_kernel<false>), dim3(static_cast<unsigned>((n_hw + kColorThreads - 1) / kColorThreads)),
-                       dim3(kColorThreads), 0, st, n_pos, pl, quad_cap, static_cast<const uint4*>(counts), lengths, nullptr,
-                       nullptr);
-    if (int rc = dif::launch_status("sliced_color_kernel")) return rc;
-    hipLaunchKernelGGL(sliced_table_kernel, dim3(1), dim3(1024), 0, st, lengths, pl, table);
-    return dif::launch_status("sliced_table_kernel");
+    if (int rc = dif::launch("sliced_color_kernel", sliced_color_kernel<false>,
+                             dif::grid_of((n_hw + kColorThreads - 1) / kColorThreads), dim3(kColorThreads), 0, st, n_pos, pl,
+                             quad_cap, static_cast<const uint4*>(counts), lengths, nullptr, nullptr)) return rc;
+    return dif::launch("sliced_table_kernel", sliced_table_kernel, dim3(1), dim3(1024), 0, st, lengths, pl, table);
 }
 
 extern "C" int dif_sliced_emit(const int32_t* rowptr, const int32_t* blkptr, int64_t n_src, int64_t row_begin,
@@ -966,15 +962,13 @@ extern "C" int dif_sliced_emit(const int32_t* rowptr, const int32_t* blkptr, int
                 "dif_sliced_emit: entries / counts must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n_hw = static_cast<int64_t>(pl.G) * pl.NT * 4;
-    hipLaunchKernelGGL((sliced_color_kernel<true>), dim3(static_cast<unsigned>((n_hw + kColorThreads - 1) / kColorThreads)),
-                       dim3(kColorThreads), 0, st, n_pos, pl, quad_cap, static_cast<const uint4*>(counts), nullptr, table,
-                       entries);
-    if (int rc = dif::launch_status("sliced_color_kernel")) return rc;
+    if (int rc = dif::launch("sliced_color_kernel", sliced_color_kernel<true>,
+                             dif::grid_of((n_hw + kColorThreads - 1) / kColorThreads), dim3(kColorThreads), 0, st, n_pos, pl,
+                             quad_cap, static_cast<const uint4*>(counts), nullptr, table, entries)) return rc;
     const int64_t n_st = static_cast<int64_t>(pl.G) * pl.NT;                 // one wave per (slot, tile)
-    hipLaunchKernelGGL(sliced_fill_kernel, dim3(static_cast<unsigned>((n_st + 3) / 4)), dim3(256), 0, st, rowptr, blkptr,
+    return dif::launch("sliced_fill_kernel", sliced_fill_kernel, dif::grid_of((n_st + 3) / 4), dim3(256), 0, st, rowptr, blkptr,
                        n_src, row_begin, n_pos, row_order, parts, pl, sorted, static_cast<const uint4*>(counts), table,
                        reinterpret_cast<uint4*>(entries));
-    return dif::launch_status("sliced_fill_kernel");
 }
 
 extern "C" int dif_sliced_prescale_f32(const float* x, int64_t ldx, const int32_t* rowptr, const float* dinv, int64_t n_src,
@@ -987,9 +981,9 @@ extern "C" int dif_sliced_prescale_f32(const float* x, int64_t ldx, const int32_
     const int64_t npad = static_cast<int64_t>(plan[6]) * plan[7];
     DIF_REQUIRE(slices == F / 4 && npad >= n_src, DIF_E_BADARG, "dif_sliced_prescale: plan does not match F / n_src");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(sliced_prescale_kernel, dim3(static_cast<unsigned>((npad + 63) / 64), (slices + kPreSlices - 1) / kPreSlices),
-                       dim3(256), 0, st, x, ldx, rowptr, dinv, n_src, npad, slices, reinterpret_cast<f32x4*>(ys));
-    return dif::launch_status("sliced_prescale_kernel");
+    return dif::launch("sliced_prescale_kernel", sliced_prescale_kernel,
+                       dif::grid_of((npad + 63) / 64, (slices + kPreSlices - 1) / kPreSlices), dim3(256), 0, st, x, ldx, rowptr,
+                       dinv, n_src, npad, slices, reinterpret_cast<f32x4*>(ys));
 }
 
 extern "C" int dif_sliced_spmm_f32(const uint16_t* entries, const int32_t* table, const int32_t* plan, const float* ys,
@@ -1014,17 +1008,7 @@ extern "C" int dif_sliced_spmm_f32(const uint16_t* entries, const int32_t* table
                          static_cast<f32x4*>(ws)};
     const uint4* e4 = reinterpret_cast<const uint4*>(entries);
     const f32x4* y4 = reinterpret_cast<const f32x4*>(ys);
-    switch (pl.R) {
-        case 1: return launch_sweep<1>(st, e4, table, y4, npad, pl, ep);
-        case 2: return launch_sweep<2>(st, e4, table, y4, npad, pl, ep);
-        case 3: return launch_sweep<3>(st, e4, table, y4, npad, pl, ep);
-        case 4: return launch_sweep<4>(st, e4, table, y4, npad, pl, ep);
-        case 5: return launch_sweep<5>(st, e4, table, y4, npad, pl, ep);
-        case 6: return launch_sweep<6>(st, e4, table, y4, npad, pl, ep);
-        case 7: return launch_sweep<7>(st, e4, table, y4, npad, pl, ep);
-        case 8: return launch_sweep<8>(st, e4, table, y4, npad, pl, ep);
-        case 9: return launch_sweep<9>(st, e4, table, y4, npad, pl, ep);
-        case 10: return launch_sweep<10>(st, e4, table, y4, npad, pl, ep);
-    }
-    return dif::fail(DIF_E_SHAPE, "dif_sliced_spmm: %d rounds per wave not covered", pl.R);
+    return dif::with_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(
+        pl.R, [&](auto R) { return launch_sweep<R>(st, e4, table, y4, npad, pl, ep); },
+        [](int r) { return dif::fail(DIF_E_SHAPE, "dif_sliced_spmm: %d rounds per wave not covered", r); });
 }

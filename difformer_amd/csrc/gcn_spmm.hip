@@ -690,14 +690,11 @@ int launch_blocked_v(hipStream_t st, const int32_t* blkptr, int64_t n_nodes, int
     const int64_t n_panels = order ? (n_quads + rpw / S - 1) / (rpw / S) : (n_rows + rpw - 1) / rpw;
     int64_t grid = n_panels < n_wg ? n_panels : n_wg;
     const bool wide = n_nodes * ldx >= (int64_t(1) << 31);
-#define DIF_BLK_LAUNCH(WIDEV, ORDV) \
-    hipLaunchKernelGGL((spmm_blocked_kernel<G, W, WPC, UNROLL, true, WIDEV, ORDV, E>), dim3(static_cast<unsigned>(grid)), \
-                       dim3(64 * kBlkWaves), 0, st, blkptr, n_nodes, n_blocks, src, val, x, ldx, row_begin, n_rows, F, attn, \
-                       lda, attn_scale, gcn_scale, tail, out, ldo, static_cast<int>(rpw), order, n_split, sw)
-    if (order) { if (wide) DIF_BLK_LAUNCH(true, true); else DIF_BLK_LAUNCH(false, true); }
-    else { if (wide) DIF_BLK_LAUNCH(true, false); else DIF_BLK_LAUNCH(false, false); }
-#undef DIF_BLK_LAUNCH
-    return dif::launch_status("spmm_blocked_kernel");
+    return dif::with_flags([&](auto WIDE, auto ORDERED) {
+        return dif::launch("spmm_blocked_kernel", spmm_blocked_kernel<G, W, WPC, UNROLL, true, WIDE, ORDERED, E>, dif::grid_of(grid),
+                           dim3(64 * kBlkWaves), 0, st, blkptr, n_nodes, n_blocks, src, val, x, ldx, row_begin, n_rows, F, attn,
+                           lda, attn_scale, gcn_scale, tail, out, ldo, static_cast<int>(rpw), order, n_split, sw);
+    }, wide, order != nullptr);
 }
 
 template <int G, int W, typename E>
@@ -720,16 +717,14 @@ int launch(bool wave_mode, hipStream_t st, const int32_t* rowptr, const int32_t*
     if (wave_mode) {
         int64_t gx = (n_rows + 3) / 4;
         if (gx > cap) gx = cap;
-        hipLaunchKernelGGL((spmm_wave_row_kernel<G, W, E>), dim3(static_cast<unsigned>(gx), gy), dim3(256), 0, st, rowptr,
-                           src, val, x, ldx, row_begin, n_rows, F, attn, lda, attn_scale, gcn_scale, tail, out, ldo);
-    } else {
-        constexpr int RPB = 256 / G;
-        int64_t gx = (n_rows + RPB - 1) / RPB;
-        if (gx > cap) gx = cap;
-        hipLaunchKernelGGL((spmm_group_row_kernel<G, W, E>), dim3(static_cast<unsigned>(gx), gy), dim3(256), 0, st,
-                           rowptr, src, val, x, ldx, row_begin, n_rows, F, attn, lda, attn_scale, gcn_scale, tail, out, ldo);
+        return dif::launch("spmm kernel", spmm_wave_row_kernel<G, W, E>, dif::grid_of(gx, gy), dim3(256), 0, st, rowptr, src, val,
+                           x, ldx, row_begin, n_rows, F, attn, lda, attn_scale, gcn_scale, tail, out, ldo);
     }
-    return dif::launch_status("spmm kernel");
+    constexpr int RPB = 256 / G;
+    int64_t gx = (n_rows + RPB - 1) / RPB;
+    if (gx > cap) gx = cap;
+    return dif::launch("spmm kernel", spmm_group_row_kernel<G, W, E>, dif::grid_of(gx, gy), dim3(256), 0, st, rowptr, src, val, x,
+                       ldx, row_begin, n_rows, F, attn, lda, attn_scale, gcn_scale, tail, out, ldo);
 }
 
 }  // namespace
@@ -739,25 +734,18 @@ static int spmm_dispatch(bool wave_mode, hipStream_t st, const int32_t* rowptr, 
                          const float* val, const E* x, int64_t ldx, int64_t row_begin, int64_t n_rows, int F,
                          const E* attn, int64_t lda, float attn_scale, float gcn_scale, const Tail<E>& tail,
                          E* out, int64_t ldo, bool vec) {
-#define DIF_SPMM(G, W) \
-    return launch<G, W, E>(wave_mode, st, rowptr, src, val, x, ldx, row_begin, n_rows, F, attn, lda, attn_scale, gcn_scale, tail, out, ldo)
-    if (vec) {
-        const int q = F / 4;
-        if (q <= 1) DIF_SPMM(1, 4);
-        if (q <= 2) DIF_SPMM(2, 4);
-        if (q <= 4) DIF_SPMM(4, 4);
-        if (q <= 8) DIF_SPMM(8, 4);
-        if (q <= 16) DIF_SPMM(16, 4);
-        if (q <= 32) DIF_SPMM(32, 4);
-        DIF_SPMM(64, 4);
-    } else {
-        if (F <= 4) DIF_SPMM(4, 1);
-        if (F <= 8) DIF_SPMM(8, 1);
-        if (F <= 16) DIF_SPMM(16, 1);
-        if (F <= 32) DIF_SPMM(32, 1);
-        DIF_SPMM(64, 1);
-    }
-#undef DIF_SPMM
+    // lane group: the smallest power of two that holds a row (of F / 4 four-element lanes when vectorised), 64 at most
+    const int need = vec ? F / 4 : F;
+    int g = vec ? 1 : 4;
+    while (g < 64 && g < need) g *= 2;
+    return dif::with_flags([&](auto VEC) {
+        return dif::with_int<1, 2, 4, 8, 16, 32, 64>(g, [&](auto G) -> int {
+            // scalar rows start at groups of four lanes: no <1, 1> and <2, 1> kernels are built
+            if constexpr (!VEC && G < 4) return dif::fail(DIF_E_SHAPE, "dif_gcn_spmm: no scalar kernel for groups of %d lanes", int(G));
+            else return launch<G, VEC ? 4 : 1, E>(wave_mode, st, rowptr, src, val, x, ldx, row_begin, n_rows, F, attn, lda, attn_scale,
+                                                  gcn_scale, tail, out, ldo);
+        }, dif::no_variant("dif_gcn_spmm"));
+    }, vec);
 }
 
 template <typename E>
@@ -795,26 +783,27 @@ static int spmm_entry(const int32_t* rowptr, const int32_t* blkptr, int n_blocks
     DIF_REQUIRE(!part || (n_blocks > 1 && vec && F <= 256 && nnz > 0), DIF_E_SHAPE,
                 "dif_gcn_spmm_part: split products run on the blocked kernel only (n_blocks > 1, F %% 4 == 0, F <= 256, aligned)");
     if (n_blocks > 1 && vec && F <= 256 && nnz > 0) {
-#define DIF_BLK(G, W) \
-    return launch_blocked<G, W, E>(st, blkptr, n_nodes, n_blocks, src, val, x, ldx, row_begin, n_rows, F, attn, lda, \
-                                   attn_scale, gcn_scale, tail, out, ldo, order, n_split, sw)
+        bool v8 = false;
         if constexpr (sizeof(E) == 2) {
             // bfloat16 rows: 8 elements per lane = 16-byte gathers (a 64-wide row is one 128-byte line)
-            auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-            const bool v8 = (F % 8 == 0) && (ldx % 8 == 0) && (ldo % 8 == 0) && (!attn || lda % 8 == 0) && a16(x) &&
-                            a16(out) && (!attn || a16(attn)) && (!tail.x0 || (tail.ldx0 % 8 == 0 && a16(tail.x0))) &&
-                            (!tail.prev || (tail.ldp % 8 == 0 && a16(tail.prev))) &&
-                            (!tail.ln_w || (a16(tail.ln_w) && a16(tail.ln_b)));
-            if (v8) {
-                if (F <= 64) DIF_BLK(8, 8);
-                if (F <= 128) DIF_BLK(16, 8);
-                DIF_BLK(32, 8);
-            }
+            auto a16 = [](const void* p) { return dif::aligned<16>(p); };
+            v8 = (F % 8 == 0) && (ldx % 8 == 0) && (ldo % 8 == 0) && (!attn || lda % 8 == 0) && a16(x) &&
+                 a16(out) && (!attn || a16(attn)) && (!tail.x0 || (tail.ldx0 % 8 == 0 && a16(tail.x0))) &&
+                 (!tail.prev || (tail.ldp % 8 == 0 && a16(tail.prev))) &&
+                 (!tail.ln_w || (a16(tail.ln_w) && a16(tail.ln_b)));
         }
-        if (F <= 64) DIF_BLK(16, 4);
-        if (F <= 128) DIF_BLK(32, 4);
-        DIF_BLK(64, 4);
-#undef DIF_BLK
+        // lanes per row: rows of up to 64 / 128 / 256 columns on lanes of 4 (or 8) elements
+        const int g = (F <= 64 ? 16 : F <= 128 ? 32 : 64) / (v8 ? 2 : 1);
+        return dif::with_flags([&](auto V8) {
+            return dif::with_int<8, 16, 32, 64>(g, [&](auto G) -> int {
+                // eight-element lanes are bfloat16-only and cover 256 columns with 32 lanes; four-element lanes start at 16
+                if constexpr (V8 ? (sizeof(E) != 2 || G > 32) : G < 16)
+                    return dif::fail(DIF_E_SHAPE, "dif_gcn_spmm: no blocked kernel for %d lanes of %d elements", int(G), V8 ? 8 : 4);
+                else
+                    return launch_blocked<G, V8 ? 8 : 4, E>(st, blkptr, n_nodes, n_blocks, src, val, x, ldx, row_begin, n_rows, F, attn,
+                                                            lda, attn_scale, gcn_scale, tail, out, ldo, order, n_split, sw);
+            }, dif::no_variant("dif_gcn_spmm"));
+        }, v8);
     }
     // row mapping: a whole wave per row pays off once a row keeps the wave's gather slots busy
     const bool wave_mode = nnz / n_nodes >= 16;

@@ -173,33 +173,28 @@ int layer_tail_entry(const T* conv, int64_t ldc, int64_t n_rows, int H, int D, c
     DIF_REQUIRE(vec || (out != conv && out != x0 && out != prev), DIF_E_BADARG,
                 "dif_layer_tail: in-place needs D % 4 == 0, D <= 512 and aligned rows");
     const int64_t cap = 8 * dif::kCUs;
-    if (vec) {
-        const int q = D / 4;
-#define DIF_TAIL2(G, V)                                                                                        \
-    do {                                                                                                       \
-        int64_t gx = (n_rows + (256 / G) - 1) / (256 / G);                                                     \
-        if (gx > cap) gx = cap;                                                                                \
-        hipLaunchKernelGGL((layer_tail_vec_kernel<G, V, T>), dim3(static_cast<unsigned>(gx)), dim3(256), 0, st, conv, \
-                           ldc, n_rows, H, D, x0, ldx0, prev, ldp, alpha, ln_weight, ln_bias, ln_eps, relu, out, ldo); \
-    } while (0)
-#define DIF_TAIL(G) DIF_TAIL2(G, 1)
-        if (q <= 1) DIF_TAIL(1);
-        else if (q <= 2) DIF_TAIL(2);
-        else if (q <= 4) DIF_TAIL(4);
-        else if (q <= 8) DIF_TAIL(8);
-        else if (q <= 16) DIF_TAIL(16);
-        else if (q <= 32) DIF_TAIL(32);
-        else if (q <= 64) DIF_TAIL(64);
-        else DIF_TAIL2(64, 2);
-#undef DIF_TAIL
-#undef DIF_TAIL2
-    } else {
+    if (!vec) {
         int64_t gx = (n_rows + 3) / 4;
         if (gx > cap) gx = cap;
-        hipLaunchKernelGGL((layer_tail_generic_kernel<T>), dim3(static_cast<unsigned>(gx)), dim3(256), 0, st, conv, ldc,
-                           n_rows, H, D, x0, ldx0, prev, ldp, alpha, ln_weight, ln_bias, ln_eps, relu, out, ldo);
+        return dif::launch("layer_tail kernel", layer_tail_generic_kernel<T>, dif::grid_of(gx), dim3(256), 0, st, conv, ldc, n_rows, H,
+                           D, x0, ldx0, prev, ldp, alpha, ln_weight, ln_bias, ln_eps, relu, out, ldo);
     }
-    return dif::launch_status("layer_tail kernel");
+    const int q = D / 4;                 // four-element lanes a row needs; beyond 64 lanes: two quads per lane
+    int g = 1;
+    while (g < 64 && g < q) g *= 2;
+    return dif::with_flags([&](auto TWO) {
+        return dif::with_int<1, 2, 4, 8, 16, 32, 64>(g, [&](auto G) -> int {
+            // two quads per lane are built for the full 64-lane group only
+            if constexpr (TWO && G < 64) return dif::fail(DIF_E_SHAPE, "dif_layer_tail: no two-quad kernel for %d lanes", int(G));
+            else {
+                int64_t gx = (n_rows + (256 / G) - 1) / (256 / G);
+                if (gx > cap) gx = cap;
+                return dif::launch("layer_tail kernel", layer_tail_vec_kernel<G, TWO ? 2 : 1, T>, dif::grid_of(gx), dim3(256), 0, st,
+                                   conv, ldc, n_rows, H, D, x0, ldx0, prev, ldp, alpha, ln_weight, ln_bias, ln_eps, relu, out, ldo,
+                                   Mix{});
+            }
+        }, dif::no_variant("dif_layer_tail"));
+    }, q > 64);
 }
 
 }  // namespace
@@ -232,19 +227,21 @@ extern "C" int dif_layer_tail_mix_f32(const float* conv, int64_t ldc, const floa
     const Mix mix = {den, ldden, conv_scale, add, lda, add_scale, rs, bv};
     const int64_t cap = 8 * dif::kCUs;
     const int q = D / 4;
-#define DIF_MIX(G, V)                                                                                              \
-    do {                                                                                                           \
-        int64_t gx = (n_rows + (256 / G) - 1) / (256 / G);                                                         \
-        if (gx > cap) gx = cap;                                                                                    \
-        hipLaunchKernelGGL((layer_tail_vec_kernel<G, V, float, true>), dim3(static_cast<unsigned>(gx)), dim3(256), 0, st, conv, \
-                           ldc, n_rows, 1, D, x0, ldx0, prev, ldp, alpha, ln_weight, ln_bias, ln_eps, relu, out, ldo, mix); \
-    } while (0)
-    if (q <= 16) DIF_MIX(16, 1);
-    else if (q <= 32) DIF_MIX(32, 1);
-    else if (q <= 64) DIF_MIX(64, 1);
-    else DIF_MIX(64, 2);
-#undef DIF_MIX
-    return dif::launch_status("layer_tail_vec_kernel<mix>");
+    int g = 16;                          // the scripts' widths: groups of 16 lanes and up
+    while (g < 64 && g < q) g *= 2;
+    return dif::with_flags([&](auto TWO) {
+        return dif::with_int<16, 32, 64>(g, [&](auto G) -> int {
+            // two quads per lane are built for the full 64-lane group only
+            if constexpr (TWO && G < 64) return dif::fail(DIF_E_SHAPE, "dif_layer_tail_mix_f32: no two-quad kernel for %d lanes", int(G));
+            else {
+                int64_t gx = (n_rows + (256 / G) - 1) / (256 / G);
+                if (gx > cap) gx = cap;
+                return dif::launch("layer_tail_vec_kernel<mix>", layer_tail_vec_kernel<G, TWO ? 2 : 1, float, true>, dif::grid_of(gx),
+                                   dim3(256), 0, st, conv, ldc, n_rows, 1, D, x0, ldx0, prev, ldp, alpha, ln_weight, ln_bias, ln_eps,
+                                   relu, out, ldo, mix);
+            }
+        }, dif::no_variant("dif_layer_tail_mix_f32"));
+    }, q > 64);
 }
 
 extern "C" int dif_layer_tail_bf16(const void* conv, int64_t ldc, int64_t n_rows, int H, int D, const void* x0,

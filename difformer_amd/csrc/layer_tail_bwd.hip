@@ -200,24 +200,15 @@ extern "C" int dif_layer_tail_bwd_f32(const float* conv, int64_t ldc, int64_t n_
         ws = static_cast<float*>(workspace);
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define DIF_TAILB(...)                                                                                                    \
-    hipLaunchKernelGGL((layer_tail_bwd_kernel<__VA_ARGS__>), dim3(blocks), dim3(256), 0, st, conv, ldc, n_rows, H, D, x0, ldx0, prev, \
-                       ldp, alpha, ln_weight, ln_bias, ln_eps, relu, grad_out, ldg, d_conv, lddc, d_x0, lddx0, d_prev, lddp, \
-                       ws, static_cast<int64_t>(2 * D))
-    switch (G) {
-        case 1: DIF_TAILB(1); break;
-        case 2: DIF_TAILB(2); break;
-        case 4: DIF_TAILB(4); break;
-        case 8: DIF_TAILB(8); break;
-        case 16: DIF_TAILB(16); break;
-        case 32: DIF_TAILB(32); break;
-        default:
-            if (D <= 256) DIF_TAILB(64);
-            else DIF_TAILB(64, 2);
-            break;
-    }
-#undef DIF_TAILB
-    if (int rc = dif::launch_status("layer_tail_bwd_kernel")) return rc;
+    if (int rc = dif::with_flags([&](auto TWO) {
+            return dif::with_int<1, 2, 4, 8, 16, 32, 64>(G, [&](auto GV) -> int {
+                // two quads per lane (rows of 257 .. 512 columns) are built for the full 64-lane group only
+                if constexpr (TWO && GV < 64) return dif::fail(DIF_E_SHAPE, "dif_layer_tail_bwd: no two-quad kernel for %d lanes", int(GV));
+                else return dif::launch("layer_tail_bwd_kernel", layer_tail_bwd_kernel<GV, TWO ? 2 : 1>, dim3(blocks), dim3(256), 0, st,
+                                        conv, ldc, n_rows, H, D, x0, ldx0, prev, ldp, alpha, ln_weight, ln_bias, ln_eps, relu,
+                                        grad_out, ldg, d_conv, lddc, d_x0, lddx0, d_prev, lddp, ws, static_cast<int64_t>(2 * D));
+            }, dif::no_variant("dif_layer_tail_bwd"));
+        }, D > 256)) return rc;
     if (!ln_weight) return 0;
     // d_ln float[2 D] = {d ln_weight, d ln_bias}: column sums of the workgroup records, fixed order
     return dif::launch_record_finalize(ws, blocks, 2 * D, 2 * D, -1, d_ln, st);

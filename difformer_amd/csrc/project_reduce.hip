@@ -308,13 +308,10 @@ int project_reduce_entry(const T* x, int64_t ldx, int64_t n_rows, int C_in, cons
     float* ws = static_cast<float*>(workspace);
     const bool exact = vec && C_in == 64 && D == 64;
     const int wvec = dif::aligned_v4<T>(Wq) && dif::aligned_v4<T>(Wk) && dif::aligned_v4<T>(Wv);   // H*D*C is a multiple of 4096 here
-    if (exact)
-        hipLaunchKernelGGL((project_reduce_kernel<true, T>), dim3(P, H), dim3(256), 0, st, x, ldx, n_rows, sh, Wq, bq, Wk,
-                           bk, Wv, bv, q_out, ldq, v_out, ldv, ws, rec, vec, wvec);
-    else
-        hipLaunchKernelGGL((project_reduce_kernel<false, T>), dim3(P, H), dim3(256), 0, st, x, ldx, n_rows, sh, Wq, bq,
-                           Wk, bk, Wv, bv, q_out, ldq, v_out, ldv, ws, rec, vec, wvec);
-    if (int rc = dif::launch_status("project_reduce_kernel")) return rc;
+    if (int rc = dif::with_flags([&](auto EXACT) {
+            return dif::launch("project_reduce_kernel", project_reduce_kernel<EXACT, T>, dim3(P, H), dim3(256), 0, st, x, ldx, n_rows,
+                               sh, Wq, bq, Wk, bk, Wv, bv, q_out, ldq, v_out, ldv, ws, rec, vec, wvec);
+        }, exact)) return rc;
     return dif::launch_record_finalize(ws, P, rec, sh.t_main, H, reduced, st);
 }
 

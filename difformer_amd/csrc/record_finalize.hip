@@ -65,8 +65,8 @@ namespace dif {
 int launch_record_finalize(const float* ws, int P, int64_t ws_stride, int t_main, int tiles, float* reduced,
                            hipStream_t st) {
     const int nb = (t_main + 63) / 64 + (tiles >= 0 ? 1 : 0);       // tiles < 0: column sums only, no scalar pair
-    hipLaunchKernelGGL(record_finalize_kernel, dim3(nb), dim3(1024), 0, st, ws, P, ws_stride, t_main, tiles, reduced);
-    return launch_status("record_finalize_kernel");
+    return dif::launch("record_finalize_kernel", record_finalize_kernel, dim3(nb), dim3(1024), 0, st, ws, P, ws_stride, t_main,
+                       tiles, reduced);
 }
 
 }  // namespace dif

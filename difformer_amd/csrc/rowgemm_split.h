@@ -149,15 +149,13 @@ inline int rowgemm_split_launch(const char* who, hipStream_t st, const float* A,
                                 int64_t ldc, const float* beta_dev, int64_t n_rows, int K, int C, float* out, int64_t ldo,
                                 const float* norm2, const float* den_vec, float den_add) {
     constexpr int kFragBytes = 2 * 8 * 4 * 64 * 16;                       // 64 KiB of fragments
-    static const hipError_t ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_split_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kFragBytes);
-    if (ok != hipSuccess) return dif::fail(static_cast<int>(ok), "%s: LDS attribute: %s", who, hipGetErrorString(ok));
+    if (int rc = dif::allow_lds<&rowgemm_split_kernel>(kFragBytes, who)) return rc;
     const int64_t n_steps = (n_rows + 15) / 16;
     int64_t gw = (n_steps + 2 * kRsWaves - 1) / (2 * kRsWaves);
     if (gw > 2 * dif::kCUs) gw = 2 * dif::kCUs;
-    hipLaunchKernelGGL(rowgemm_split_kernel, dim3(static_cast<unsigned>(gw)), dim3(64 * kRsWaves), kFragBytes, st, A, lda, Mat, ldm,
-                       mat_t, mat_scale, bias, r, u, u_scale, Cin, ldc, beta_dev, n_rows, K, C, out, ldo, norm2, den_vec, den_add);
-    return dif::launch_status("rowgemm_split_kernel");
+    return dif::launch("rowgemm_split_kernel", rowgemm_split_kernel, dif::grid_of(gw), dim3(64 * kRsWaves), kFragBytes, st, A, lda,
+                       Mat, ldm, mat_t, mat_scale, bias, r, u, u_scale, Cin, ldc, beta_dev, n_rows, K, C, out, ldo, norm2, den_vec,
+                       den_add);
 }
 
 }  // namespace

@@ -234,15 +234,15 @@ extern "C" int dif_gram_bg_f32(const float* x, int64_t ldx, int64_t n_rows, int 
                     "dif_gram_bg: rows of x must be 16-byte aligned (slice-major copy: ldx = rows per slice >= n_rows)");
         DIF_REQUIRE(workspace_bytes >= dif_gram_bg_workspace_bytes(n_rows, C), DIF_E_WORKSPACE, "dif_gram_bg: workspace too small");
         P = bg_chunks(n_rows);
-        if (rscale) hipLaunchKernelGGL(gram_bg_kernel<true>, dim3(P), dim3(64), 0, st, x, ldx, n_rows, C, ws, rec_stride(C), rscale);
-        else hipLaunchKernelGGL(gram_bg_kernel<false>, dim3(P), dim3(64), 0, st, x, ldx, n_rows, C, ws, rec_stride(C), rscale);
-        if (int rc = dif::launch_status("gram_bg_kernel")) return rc;
+        if (int rc = dif::with_flags([&](auto SC) {
+                return dif::launch("gram_bg_kernel", gram_bg_kernel<SC>, dim3(P), dim3(64), 0, st, x, ldx, n_rows, C, ws, rec_stride(C),
+                                   rscale);
+            }, rscale != nullptr)) return rc;
     } else {
         DIF_REQUIRE(workspace_bytes >= static_cast<size_t>(C * C + C) * sizeof(float), DIF_E_WORKSPACE, "dif_gram_bg: record too small");
     }
-    hipLaunchKernelGGL(finalize_bg_kernel, dim3(kB * kB / 64), dim3(64), 0, st, ws, P, rec_stride(C), C,
+    return dif::launch("finalize_bg_kernel", finalize_bg_kernel, dim3(kB * kB / 64), dim3(64), 0, st, ws, P, rec_stride(C), C,
                        static_cast<float>(n_global), sfac, gt, reinterpret_cast<double*>(gt + kB * kB));
-    return dif::launch_status("finalize_bg_kernel");
 }
 
 // pt = P~ = W~q^T W~k, vtt = V~^T, st = [W~q^T W~q ; W~k^T W~k]: float[80 * 80] (x 2 for st), zero padded, augmented index
@@ -260,8 +260,8 @@ extern "C" int dif_simple_coeffs_bg_f32(const float* gt, const float* pt, const 
     float* scal = scratch + kB * kB;
     const double* npart = reinterpret_cast<const double*>(gt + kB * kB);
     constexpr int kT = kB / 16;
-    hipLaunchKernelGGL((coeffs_bg_kernel<0>), dim3(kT * kT + 1), dim3(64), 0, s, gt, pt, vtt, st, C, D, attn_scale, tt, scal, npart, coef);
-    if (int rc = dif::launch_status("coeffs_bg_kernel<0>")) return rc;
-    hipLaunchKernelGGL((coeffs_bg_kernel<1>), dim3(kT * kT), dim3(64), 0, s, gt, pt, vtt, st, C, D, attn_scale, tt, scal, npart, coef);
-    return dif::launch_status("coeffs_bg_kernel<1>");
+    if (int rc = dif::launch("coeffs_bg_kernel<0>", coeffs_bg_kernel<0>, dim3(kT * kT + 1), dim3(64), 0, s, gt, pt, vtt, st, C, D,
+                             attn_scale, tt, scal, npart, coef)) return rc;
+    return dif::launch("coeffs_bg_kernel<1>", coeffs_bg_kernel<1>, dim3(kT * kT), dim3(64), 0, s, gt, pt, vtt, st, C, D, attn_scale,
+                       tt, scal, npart, coef);
 }

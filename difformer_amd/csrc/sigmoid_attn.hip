@@ -411,36 +411,19 @@ int sigmoid_attn(const char* who, const T* q, int64_t ldq, const T* k, int64_t l
     float* part = static_cast<float*>(workspace);
     float* pden = (S > 1) ? part + static_cast<size_t>(S) * N * H * D : nullptr;
     dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(gy), S), block(512);
-#define DIF_LAUNCH_SIG(V, Q) \
-    hipLaunchKernelGGL((sigmoid_attn_kernel<V, Q, false, T>), grid, block, 0, st, q, ldq, k, ldk, v, ldv, N, L, H, M, D, out, \
-                       ldo, part, pden, den, nullptr, nullptr, 0)
-    if constexpr (std::is_same<T, float>::value) {
-        if (split_kernel) {                        // both contractions on split-bfloat16 operands (sigmoid_attn_kernel<..., SPLIT>)
-            hipLaunchKernelGGL((sigmoid_attn_kernel<true, true, false, T, true>), grid, block, 0, st, q, ldq, k, ldk, v, ldv, N, L, H, M, D,
-                               out, ldo, part, pden, den, nullptr, nullptr, 0);
-            if (int rc = dif::launch_status("sigmoid_attn_kernel<split>")) return rc;
-            if (S > 1) {
-                int64_t g = (N * H * D + 255) / 256;
-                if (g > 8 * dif::kCUs) g = 8 * dif::kCUs;
-                hipLaunchKernelGGL(sigmoid_combine_kernel<T>, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, part, pden, N, H, D, S,
-                                   out, ldo, den);
-                return dif::launch_status("sigmoid_combine_kernel");
-            }
-            return 0;
-        }
-    }
-    if (vec && qreg) DIF_LAUNCH_SIG(true, true);
-    else if (vec) DIF_LAUNCH_SIG(true, false);
-    else if (qreg) DIF_LAUNCH_SIG(false, true);
-    else DIF_LAUNCH_SIG(false, false);
-#undef DIF_LAUNCH_SIG
-    if (int rc = dif::launch_status("sigmoid_attn_kernel")) return rc;
+    if (int rc = dif::with_flags([&](auto V, auto Q, auto SPLIT) -> int {
+            // both contractions on split-bfloat16 operands (sigmoid_attn_kernel<..., SPLIT>): built for float32 rows held in
+            // registers and loaded as vectors only
+            if constexpr (SPLIT && !(V && Q && std::is_same<T, float>::value)) return dif::fail(DIF_E_SHAPE, "%s: no split kernel for this layout", who);
+            else return dif::launch(SPLIT ? "sigmoid_attn_kernel<split>" : "sigmoid_attn_kernel", sigmoid_attn_kernel<V, Q, false, T, SPLIT>,
+                                    grid, block, 0, st, q, ldq, k, ldk, v, ldv, N, L, H, M, D, out, ldo, part, pden, den, nullptr,
+                                    nullptr, 0);
+        }, vec, qreg, split_kernel)) return rc;
     if (S > 1) {
         int64_t g = (N * H * D + 255) / 256;
         if (g > 8 * dif::kCUs) g = 8 * dif::kCUs;
-        hipLaunchKernelGGL(sigmoid_combine_kernel<T>, dim3(static_cast<unsigned>(g)), dim3(256), 0, st, part, pden, N, H, D, S,
-                           out, ldo, den);
-        return dif::launch_status("sigmoid_combine_kernel");
+        return dif::launch("sigmoid_combine_kernel", sigmoid_combine_kernel<T>, dif::grid_of(g), dim3(256), 0, st, part, pden, N, H,
+                           D, S, out, ldo, den);
     }
     return 0;
 }
@@ -494,15 +477,10 @@ static int batched_sigmoid_entry(const float* q, int64_t ldq, const float* k, in
     const bool qreg = (M <= 64);
     hipStream_t st = static_cast<hipStream_t>(stream);
     dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(gy), static_cast<unsigned>(max_nodes)), block(512);
-#define DIF_LAUNCH_SEG(V, Q) \
-    hipLaunchKernelGGL((sigmoid_attn_kernel<V, Q, true>), grid, block, 0, st, q, ldq, k, ldk, v, ldv, int64_t{0}, \
-                       int64_t{0}, H, M, D, out, ldo, nullptr, nullptr, den, ranked_first, pos_count, n_graphs)
-    if (vec && qreg) DIF_LAUNCH_SEG(true, true);
-    else if (vec) DIF_LAUNCH_SEG(true, false);
-    else if (qreg) DIF_LAUNCH_SEG(false, true);
-    else DIF_LAUNCH_SEG(false, false);
-#undef DIF_LAUNCH_SEG
-    return dif::launch_status("sigmoid_attn_kernel<batched>");
+    return dif::with_flags([&](auto V, auto Q) {
+        return dif::launch("sigmoid_attn_kernel<batched>", sigmoid_attn_kernel<V, Q, true>, grid, block, 0, st, q, ldq, k, ldk, v, ldv,
+                           int64_t{0}, int64_t{0}, H, M, D, out, ldo, nullptr, nullptr, den, ranked_first, pos_count, n_graphs);
+    }, vec, qreg);
 }
 
 extern "C" int dif_batched_sigmoid_attn_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,

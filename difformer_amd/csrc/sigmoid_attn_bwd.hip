@@ -461,9 +461,8 @@ extern "C" int dif_sigmoid_attn_bwd_f32(const float* q, int64_t ldq, const float
     }
     int64_t pg = (N * H * 16 + 255) / 256;
     if (pg > 8 * dif::kCUs) pg = 8 * dif::kCUs;
-    hipLaunchKernelGGL(sigmoid_bwd_prep_kernel, dim3(static_cast<unsigned>(pg)), dim3(256), 0, st, g, ldg, out, ldo, den, N, H, D,
-                       cinv, delta);
-    if (int rc = dif::launch_status("sigmoid_bwd_prep_kernel")) return rc;
+    if (int rc = dif::launch("sigmoid_bwd_prep_kernel", sigmoid_bwd_prep_kernel, dif::grid_of(pg), dim3(256), 0, st, g, ldg, out,
+                             ldo, den, N, H, D, cinv, delta)) return rc;
     auto al = [](const void* p, int64_t ld) { return ld % 4 == 0 && dif::aligned16(p); };
     const bool vec = (M % 4 == 0) && (D % 4 == 0) && al(q, ldq) && al(k, ldk) && al(v, ldv) && al(g, ldg);
     // split-bfloat16 operands on the bf16 matrix core (sigmoid_bwd_kernel<..., SPLIT>): OPT-IN (DIFFORMER_SIGMOID_BWD_SPLIT=1).
@@ -475,34 +474,25 @@ extern "C" int dif_sigmoid_attn_bwd_f32(const float* q, int64_t ldq, const float
     // dQ: stationary queries (q, g), swept keys (k, v)
     {
         dim3 grid(static_cast<unsigned>((N + kXGroup - 1) / kXGroup), H, S0), block(512);
-        if (split && vec) hipLaunchKernelGGL((sigmoid_bwd_kernel<0, true, false, true>), grid, block, 0, st, q, ldq, g, ldg, k, ldk, v, ldv,
-                                             cinv, delta, N, L, H, M, D, dq, lddq, nullptr, int64_t{0}, pq, nullptr);
-        else if (split) hipLaunchKernelGGL((sigmoid_bwd_kernel<0, false, false, true>), grid, block, 0, st, q, ldq, g, ldg, k, ldk, v, ldv,
-                                           cinv, delta, N, L, H, M, D, dq, lddq, nullptr, int64_t{0}, pq, nullptr);
-        else if (vec) hipLaunchKernelGGL((sigmoid_bwd_kernel<0, true>), grid, block, 0, st, q, ldq, g, ldg, k, ldk, v, ldv, cinv, delta,
-                                    N, L, H, M, D, dq, lddq, nullptr, int64_t{0}, pq, nullptr);
-        else hipLaunchKernelGGL((sigmoid_bwd_kernel<0, false>), grid, block, 0, st, q, ldq, g, ldg, k, ldk, v, ldv, cinv, delta,
-                                N, L, H, M, D, dq, lddq, nullptr, int64_t{0}, pq, nullptr);
-        if (int rc = dif::launch_status("sigmoid_bwd_kernel<dQ>")) return rc;
+        if (int rc = dif::with_flags([&](auto VEC, auto SPLIT) {
+                return dif::launch("sigmoid_bwd_kernel<dQ>", sigmoid_bwd_kernel<0, VEC, false, SPLIT>, grid, block, 0, st, q, ldq, g, ldg,
+                                   k, ldk, v, ldv, cinv, delta, N, L, H, M, D, dq, lddq, nullptr, int64_t{0}, pq, nullptr, nullptr,
+                                   nullptr);
+            }, vec, split)) return rc;
     }
     // dK, dV: stationary keys (k, v), swept queries (q, g)
     {
         dim3 grid(static_cast<unsigned>((L + kXGroup - 1) / kXGroup), H, S1), block(512);
-        if (split && vec) hipLaunchKernelGGL((sigmoid_bwd_kernel<1, true, false, true>), grid, block, 0, st, k, ldk, v, ldv, q, ldq, g, ldg,
-                                             cinv, delta, L, N, H, M, D, dk, lddk, dv, lddv, pk, pv);
-        else if (split) hipLaunchKernelGGL((sigmoid_bwd_kernel<1, false, false, true>), grid, block, 0, st, k, ldk, v, ldv, q, ldq, g, ldg,
-                                           cinv, delta, L, N, H, M, D, dk, lddk, dv, lddv, pk, pv);
-        else if (vec) hipLaunchKernelGGL((sigmoid_bwd_kernel<1, true>), grid, block, 0, st, k, ldk, v, ldv, q, ldq, g, ldg, cinv, delta,
-                                    L, N, H, M, D, dk, lddk, dv, lddv, pk, pv);
-        else hipLaunchKernelGGL((sigmoid_bwd_kernel<1, false>), grid, block, 0, st, k, ldk, v, ldv, q, ldq, g, ldg, cinv, delta,
-                                L, N, H, M, D, dk, lddk, dv, lddv, pk, pv);
-        if (int rc = dif::launch_status("sigmoid_bwd_kernel<dK,dV>")) return rc;
+        if (int rc = dif::with_flags([&](auto VEC, auto SPLIT) {
+                return dif::launch("sigmoid_bwd_kernel<dK,dV>", sigmoid_bwd_kernel<1, VEC, false, SPLIT>, grid, block, 0, st, k, ldk, v,
+                                   ldv, q, ldq, g, ldg, cinv, delta, L, N, H, M, D, dk, lddk, dv, lddv, pk, pv, nullptr, nullptr);
+            }, vec, split)) return rc;
     }
     auto combine = [&](const float* part, int S, int64_t rows, int width, float* o, int64_t ldo_) -> int {
         int64_t gsz = (rows * width + 255) / 256;
         if (gsz > 8 * dif::kCUs) gsz = 8 * dif::kCUs;
-        hipLaunchKernelGGL(sum_parts_kernel, dim3(static_cast<unsigned>(gsz)), dim3(256), 0, st, part, S, rows, width, o, ldo_);
-        return dif::launch_status("sum_parts_kernel");
+        return dif::launch("sum_parts_kernel", sum_parts_kernel, dif::grid_of(gsz), dim3(256), 0, st, part, S, rows, width, o,
+                           ldo_);
     };
     if (S0 > 1) if (int rc = combine(pq, S0, N, H * M, dq, lddq)) return rc;
     if (S1 > 1) {
@@ -542,21 +532,17 @@ extern "C" int dif_batched_sigmoid_attn_bwd_f32(const float* q, int64_t ldq, con
     float* delta = reinterpret_cast<float*>(w + align16(static_cast<size_t>(N) * H * sizeof(float)));
     int64_t pg = (N * H * 16 + 255) / 256;
     if (pg > 8 * dif::kCUs) pg = 8 * dif::kCUs;
-    hipLaunchKernelGGL(sigmoid_bwd_prep_kernel, dim3(static_cast<unsigned>(pg)), dim3(256), 0, st, g, ldg, out, ldo, den, N, H, D,
-                       cinv, delta);
-    if (int rc = dif::launch_status("sigmoid_bwd_prep_kernel")) return rc;
+    if (int rc = dif::launch("sigmoid_bwd_prep_kernel", sigmoid_bwd_prep_kernel, dif::grid_of(pg), dim3(256), 0, st, g, ldg, out,
+                             ldo, den, N, H, D, cinv, delta)) return rc;
     auto al = [](const void* p, int64_t ld) { return ld % 4 == 0 && dif::aligned16(p); };
     const bool vec = (M % 4 == 0) && (D % 4 == 0) && al(q, ldq) && al(k, ldk) && al(v, ldv) && al(g, ldg);
     dim3 grid(static_cast<unsigned>((n_graphs + kXGroup - 1) / kXGroup), H, static_cast<unsigned>(max_nodes)), block(512);
-    if (vec) hipLaunchKernelGGL((sigmoid_bwd_kernel<0, true, true>), grid, block, 0, st, q, ldq, g, ldg, k, ldk, v, ldv, cinv, delta,
-                                int64_t{0}, int64_t{0}, H, M, D, dq, lddq, nullptr, int64_t{0}, nullptr, nullptr, ranked_first,
-                                pos_count);
-    else hipLaunchKernelGGL((sigmoid_bwd_kernel<0, false, true>), grid, block, 0, st, q, ldq, g, ldg, k, ldk, v, ldv, cinv, delta,
-                            int64_t{0}, int64_t{0}, H, M, D, dq, lddq, nullptr, int64_t{0}, nullptr, nullptr, ranked_first, pos_count);
-    if (int rc = dif::launch_status("sigmoid_bwd_kernel<dQ, batched>")) return rc;
-    if (vec) hipLaunchKernelGGL((sigmoid_bwd_kernel<1, true, true>), grid, block, 0, st, k, ldk, v, ldv, q, ldq, g, ldg, cinv, delta,
-                                int64_t{0}, int64_t{0}, H, M, D, dk, lddk, dv, lddv, nullptr, nullptr, ranked_first, pos_count);
-    else hipLaunchKernelGGL((sigmoid_bwd_kernel<1, false, true>), grid, block, 0, st, k, ldk, v, ldv, q, ldq, g, ldg, cinv, delta,
-                            int64_t{0}, int64_t{0}, H, M, D, dk, lddk, dv, lddv, nullptr, nullptr, ranked_first, pos_count);
-    return dif::launch_status("sigmoid_bwd_kernel<dK dV, batched>");
+    return dif::with_flags([&](auto VEC) -> int {
+        if (int rc = dif::launch("sigmoid_bwd_kernel<dQ, batched>", sigmoid_bwd_kernel<0, VEC, true>, grid, block, 0, st, q, ldq, g,
+                                 ldg, k, ldk, v, ldv, cinv, delta, int64_t{0}, int64_t{0}, H, M, D, dq, lddq, nullptr, int64_t{0},
+                                 nullptr, nullptr, ranked_first, pos_count)) return rc;
+        return dif::launch("sigmoid_bwd_kernel<dK dV, batched>", sigmoid_bwd_kernel<1, VEC, true>, grid, block, 0, st, k, ldk, v, ldv,
+                           q, ldq, g, ldg, cinv, delta, int64_t{0}, int64_t{0}, H, M, D, dk, lddk, dv, lddv, nullptr, nullptr,
+                           ranked_first, pos_count);
+    }, vec);
 }

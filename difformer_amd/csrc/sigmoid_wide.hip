@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void sigw_pack_kernel(const float* __restrict_
         const int r = threadIdx.x >> 3;
         const int64_t row = 32ll * t + r;
         const float* src = x + row * ld + static_cast<int64_t>(h) * creal;
-        const bool vec = (creal % 4 == 0) && (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0);
+        const bool vec = (creal % 4 == 0) && (ld % 4 == 0) && dif::aligned<16>(x);
         float inv = 1.0f;
         if (rowdiv && row < R) inv = rowdiv[row * H + h];
 #pragma unroll
@@ -207,7 +207,7 @@ __device__ __forceinline__ void store_acc(const f32x4 (&o)[2 * KS], float den_to
             const float sc = w.normalize ? 1.0f / den_tot : 1.0f;
             float* dst = w.out + row * w.ldo + static_cast<int64_t>(h) * w.cout;
             const float* add = w.coladd ? w.coladd + static_cast<int64_t>(h) * w.cout : nullptr;
-            const bool vec = (w.cout % 4 == 0) && (w.ldo % 4 == 0) && (reinterpret_cast<uintptr_t>(w.out) & 15u) == 0;
+            const bool vec = (w.cout % 4 == 0) && (w.ldo % 4 == 0) && dif::aligned<16>(w.out);
 #pragma unroll
             for (int ct = 0; ct < 2 * KS; ++ct) {
                 const int c = 16 * ct + 4 * lg;
@@ -555,67 +555,46 @@ SweepPlan plan_sweep(int64_t NX, int64_t NY, int H, int KS, int rows_per_wg, boo
     return p;
 }
 
-template <typename K>
-int set_lds(K kernel, int bytes, const char* who) {
-    const hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (he != hipSuccess) return dif::fail(static_cast<int>(he), "%s: LDS attribute: %s", who, hipGetErrorString(he));
-    return 0;
-}
-
 int launch_pack(const float* x, int64_t ld, int64_t R, int creal, int H, int KS, const float* rowdiv, const float* colsub, bf16x8* rowp,
                 bf16x8* colp, hipStream_t st) {
     const int T = static_cast<int>((R + 31) / 32);
-    hipLaunchKernelGGL(sigw_pack_kernel<kNP>, dim3(T, H, (KS + 1) / 2), dim3(256), 0, st, x, ld, R, creal, H, KS, rowdiv, colsub, rowp, colp,
-                       T);
-    return dif::launch_status("sigw_pack_kernel");
+    return dif::launch("sigw_pack_kernel", sigw_pack_kernel<kNP>, dim3(T, H, (KS + 1) / 2), dim3(256), 0, st, x, ld, R, creal, H,
+                       KS, rowdiv, colsub, rowp, colp, T);
 }
 
 template <int KS>
 int launch_fwd_t(const FwdArgs& a, const SweepPlan& p, hipStream_t st) {
     constexpr int lds = 2 * kNP * 2 * KS * 1024;
     constexpr int W = fwd_waves_c(KS), QT = fwd_qt_c(KS);
-    static const int rc = set_lds(&sigw_fwd_kernel<KS, kNP, W, QT>, lds, "sigw_fwd");
-    if (rc) return rc;
-    hipLaunchKernelGGL((sigw_fwd_kernel<KS, kNP, W, QT>), dim3(static_cast<unsigned>(p.gx), a.H, p.S), dim3(64 * W), lds, st, a);
-    return dif::launch_status("sigw_fwd_kernel");
+    if (int rc = dif::allow_lds<&sigw_fwd_kernel<KS, kNP, W, QT>>(lds, "sigw_fwd")) return rc;
+    return dif::launch("sigw_fwd_kernel", sigw_fwd_kernel<KS, kNP, W, QT>, dif::grid_of(p.gx, a.H, p.S), dim3(64 * W), lds, st, a);
 }
 template <int KS, bool DSTREAM>
 int launch_bwd_t(const BwdArgs& a, const SweepPlan& p, hipStream_t st) {
     constexpr int lds = 2 * kNP * 2 * KS * 1024;
-    static const int rc = set_lds(&sigw_bwd_kernel<KS, kNP, kBwdWaves, DSTREAM>, lds, "sigw_bwd");
-    if (rc) return rc;
-    hipLaunchKernelGGL((sigw_bwd_kernel<KS, kNP, kBwdWaves, DSTREAM>), dim3(static_cast<unsigned>(p.gx), a.H, p.S), dim3(64 * kBwdWaves),
-                       lds, st, a);
-    return dif::launch_status("sigw_bwd_kernel");
+    if (int rc = dif::allow_lds<&sigw_bwd_kernel<KS, kNP, kBwdWaves, DSTREAM>>(lds, "sigw_bwd")) return rc;
+    return dif::launch("sigw_bwd_kernel", sigw_bwd_kernel<KS, kNP, kBwdWaves, DSTREAM>, dif::grid_of(p.gx, a.H, p.S),
+                       dim3(64 * kBwdWaves), lds, st, a);
 }
 
 int launch_fwd(int KS, const FwdArgs& a, const SweepPlan& p, hipStream_t st) {
-    switch (KS) {
-#define DIF_CASE(K) case K: return launch_fwd_t<K>(a, p, st);
-        DIF_CASE(2) DIF_CASE(3) DIF_CASE(4) DIF_CASE(5) DIF_CASE(6) DIF_CASE(7) DIF_CASE(8) DIF_CASE(9) DIF_CASE(10)
-        DIF_CASE(11) DIF_CASE(12) DIF_CASE(13) DIF_CASE(14) DIF_CASE(15) DIF_CASE(16)
-#undef DIF_CASE
-    }
-    return dif::fail(DIF_E_SHAPE, "sigmoid attention (wide heads): %d columns per head not covered", 32 * KS);
+    return dif::with_int<2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(
+        KS, [&](auto K) { return launch_fwd_t<K>(a, p, st); },
+        [](int ks) { return dif::fail(DIF_E_SHAPE, "sigmoid attention (wide heads): %d columns per head not covered", 32 * ks); });
 }
 template <bool DSTREAM>
 int launch_bwd(int KS, const BwdArgs& a, const SweepPlan& p, hipStream_t st) {
-    switch (KS) {
-#define DIF_CASE(K) case K: return launch_bwd_t<K, DSTREAM>(a, p, st);
-        DIF_CASE(3) DIF_CASE(4) DIF_CASE(5) DIF_CASE(6) DIF_CASE(7) DIF_CASE(8) DIF_CASE(9) DIF_CASE(10)
-        DIF_CASE(11) DIF_CASE(12) DIF_CASE(13) DIF_CASE(14) DIF_CASE(15) DIF_CASE(16)
-#undef DIF_CASE
-    }
-    return dif::fail(DIF_E_SHAPE, "sigmoid attention backward (wide heads): %d columns per head not covered", 32 * KS);
+    return dif::with_int<3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(
+        KS, [&](auto K) { return launch_bwd_t<K, DSTREAM>(a, p, st); },
+        [](int ks) { return dif::fail(DIF_E_SHAPE, "sigmoid attention backward (wide heads): %d columns per head not covered", 32 * ks); });
 }
 
 int launch_combine(const SweepPlan& p, const SweepOut& w, int64_t NX, int H, int KS, hipStream_t st) {
     if (p.S == 1) return 0;
     int64_t gr = (NX * H * ((w.cout + 3) / 4) + 255) / 256;
     if (gr > 8 * dif::kCUs) gr = 8 * dif::kCUs;
-    hipLaunchKernelGGL(sigw_combine_kernel, dim3(static_cast<unsigned>(gr)), dim3(256), 0, st, w.part, w.pden, NX, p.NXPAD, H, 32 * KS,
-                       w.cout, p.S, w.out, w.ldo, w.den_out, w.normalize, w.coladd);
-    return dif::launch_status("sigw_combine_kernel");
+    return dif::launch("sigw_combine_kernel", sigw_combine_kernel, dif::grid_of(gr), dim3(256), 0, st, w.part, w.pden, NX, p.NXPAD,
+                       H, 32 * KS, w.cout, p.S, w.out, w.ldo, w.den_out, w.normalize, w.coladd);
 }
 
 // cmean [H][D] = column means of v; partial: ceil(L / 128) x H D floats
@@ -624,10 +603,10 @@ inline size_t colmean_bytes(int64_t L, int H, int D) {
 }
 int launch_colmean(const float* v, int64_t ldv, int64_t L, int H, int D, float* partial, float* cmean, hipStream_t st) {
     const int blocks = static_cast<int>(colsum_blocks(L));
-    hipLaunchKernelGGL(sigw_colsum_kernel, dim3(blocks), dim3(256), 0, st, v, ldv, L, H * D, partial);
-    if (int rc = dif::launch_status("sigw_colsum_kernel")) return rc;
-    hipLaunchKernelGGL(sigw_colmean_kernel, dim3((H * D + 63) / 64), dim3(256), 0, st, partial, blocks, L, H * D, cmean);
-    return dif::launch_status("sigw_colmean_kernel");
+    if (int rc = dif::launch("sigw_colsum_kernel", sigw_colsum_kernel, dim3(blocks), dim3(256), 0, st, v, ldv, L, H * D,
+                             partial)) return rc;
+    return dif::launch("sigw_colmean_kernel", sigw_colmean_kernel, dim3((H * D + 63) / 64), dim3(256), 0, st, partial, blocks, L,
+                       H * D, cmean);
 }
 
 // carve `bytes` out of the workspace
@@ -739,9 +718,8 @@ int sigw_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const flo
     float* cmean = static_cast<float*>(cv.take(static_cast<size_t>(H) * D * sizeof(float)));
     float* part = reinterpret_cast<float*>(cv.p);
     if (int rc = launch_colmean(v, ldv, L, H, D, cpart, cmean, st)) return rc;
-    hipLaunchKernelGGL(sigw_delta_kernel, dim3(static_cast<unsigned>((ndpad * H + 3) / 4)), dim3(256), 0, st, g, ldg, out, ldo, den, cmean,
-                       N, ndpad, H, D, delta);
-    if (int rc = dif::launch_status("sigw_delta_kernel")) return rc;
+    if (int rc = dif::launch("sigw_delta_kernel", sigw_delta_kernel, dif::grid_of((ndpad * H + 3) / 4), dim3(256), 0, st, g, ldg,
+                             out, ldo, den, cmean, N, ndpad, H, D, delta)) return rc;
     if (int rc = launch_pack(q, ldq, N, M, H, KS, nullptr, nullptr, qr, qc, st)) return rc;
     if (int rc = launch_pack(k, ldk, L, M, H, KS, nullptr, nullptr, kr, kc, st)) return rc;
     if (int rc = launch_pack(v, ldv, L, D, H, KS, nullptr, cmean, vr, nullptr, st)) return rc;       // centred: T - delta~ = g~.(v - c) - g~.(out - c)

@@ -533,18 +533,16 @@ int simple_reduce_entry(const T* q, int64_t ldq, const T* k, int64_t ldk, const 
         if (H == 1 && vec && sh.tiles >= 2 && sh.MT <= 8 && sh.DT <= 2 && n_rows >= 4096 && !dif::exact_fp32()) {
             const int64_t slabs = (n_rows + kSlabRows - 1) / kSlabRows;
             const int Ps = static_cast<int>(slabs < P ? slabs : P);
-            hipLaunchKernelGGL(reduce_slab_kernel, dim3(Ps, (sh.MT + 1) / 2), dim3(256), 0, st, q, ldq, k, ldk, v, ldv, n_rows, M, D, ws, rec,
-                               sh.t_main);
-            if (int rc = dif::launch_status("reduce_slab_kernel")) return rc;
+            if (int rc = dif::launch("reduce_slab_kernel", reduce_slab_kernel, dim3(Ps, (sh.MT + 1) / 2), dim3(256), 0, st, q, ldq,
+                                     k, ldk, v, ldv, n_rows, M, D, ws, rec, sh.t_main)) return rc;
             return dif::launch_record_finalize(ws, Ps, rec, sh.t_main, sh.tiles, reduced, st);
         }
     }
     dim3 grid(P, sh.tiles), block(256);
-    if (vec)
-        hipLaunchKernelGGL((simple_reduce_kernel<true, T>), grid, block, 0, st, q, ldq, k, ldk, v, ldv, n_rows, sh, ws, rec);
-    else
-        hipLaunchKernelGGL((simple_reduce_kernel<false, T>), grid, block, 0, st, q, ldq, k, ldk, v, ldv, n_rows, sh, ws, rec);
-    if (int rc = dif::launch_status("simple_reduce_kernel")) return rc;
+    if (int rc = dif::with_flags([&](auto VEC) {
+            return dif::launch("simple_reduce_kernel", simple_reduce_kernel<VEC, T>, grid, block, 0, st, q, ldq, k, ldk, v, ldv, n_rows,
+                               sh, ws, rec);
+        }, vec)) return rc;
     return dif::launch_record_finalize(ws, P, rec, sh.t_main, sh.tiles, reduced, st);
 }
 
@@ -582,20 +580,13 @@ int simple_apply_entry(const T* q, int64_t ldq, const float* reduced, int64_t n_
         hipStream_t stw = static_cast<hipStream_t>(stream);
         dim3 gridw(static_cast<unsigned>(gxw), sh.DT, H), blockw(64 * kWideWaves);
         const float nfw = static_cast<float>(n_global);
-        // dynamic LDS beyond 64 KiB must be allowed once per kernel (set to the largest case, M = 512)
+        // dynamic LDS beyond 64 KiB must be allowed per kernel (set to the largest case, M = 512)
         constexpr int kWideLdsMax = (kTile * (8 * kTile + 4) + 8 * kTile) * static_cast<int>(sizeof(float));
-        static const hipError_t allowed[2] = {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&simple_apply_wide_kernel<false, T>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kWideLdsMax),
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&simple_apply_wide_kernel<true, T>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kWideLdsMax)};
-        const hipError_t he = allowed[vec ? 1 : 0];
-        if (he != hipSuccess) return dif::fail(static_cast<int>(he), "dif_simple_apply: LDS attribute: %s", hipGetErrorString(he));
-        if (vec)
-            hipLaunchKernelGGL((simple_apply_wide_kernel<true, T>), gridw, blockw, lds, stw, q, ldq, reduced, n_rows, nfw, sh, out, ldo);
-        else
-            hipLaunchKernelGGL((simple_apply_wide_kernel<false, T>), gridw, blockw, lds, stw, q, ldq, reduced, n_rows, nfw, sh, out, ldo);
-        return dif::launch_status("simple_apply_wide_kernel");
+        return dif::with_flags([&](auto VEC) -> int {
+            if (int rc = dif::allow_lds<&simple_apply_wide_kernel<VEC, T>>(kWideLdsMax, "dif_simple_apply")) return rc;
+            return dif::launch("simple_apply_wide_kernel", simple_apply_wide_kernel<VEC, T>, gridw, blockw, lds, stw, q, ldq, reduced,
+                               n_rows, nfw, sh, out, ldo);
+        }, vec);
     }
     int64_t gx = (n_steps + 3) / 4;
     const int64_t cap = 3 * dif::kCUs;  // persistent: the per-wave fragment prologue is paid once per ~3+ steps
@@ -604,14 +595,10 @@ int simple_apply_entry(const T* q, int64_t ldq, const float* reduced, int64_t n_
     hipStream_t st = static_cast<hipStream_t>(stream);
     dim3 grid(static_cast<unsigned>(gx), H), block(256);
     const float nf = static_cast<float>(n_global);
-#define DIF_LAUNCH_APPLY(V, S) \
-    hipLaunchKernelGGL((simple_apply_kernel<V, S, T>), grid, block, 0, st, q, ldq, reduced, n_rows, nf, sh, out, ldo)
-    if (vec && single) DIF_LAUNCH_APPLY(true, true);
-    else if (vec) DIF_LAUNCH_APPLY(true, false);
-    else if (single) DIF_LAUNCH_APPLY(false, true);
-    else DIF_LAUNCH_APPLY(false, false);
-#undef DIF_LAUNCH_APPLY
-    return dif::launch_status("simple_apply_kernel");
+    return dif::with_flags([&](auto VEC, auto SINGLE) {
+        return dif::launch("simple_apply_kernel", simple_apply_kernel<VEC, SINGLE, T>, grid, block, 0, st, q, ldq, reduced, n_rows, nf,
+                           sh, out, ldo);
+    }, vec, single);
 }
 
 }  // namespace
@@ -907,14 +894,15 @@ extern "C" int dif_gram_sym_f32(const float* x, int64_t ldx, int64_t n_rows, int
     const int Ps = gram_slab_chunks(n_rows, C);
     if (vec && C > 64 && sh.MT <= kSlabMaxMT && n_rows >= 4096 && !dif::exact_fp32() &&
         workspace_bytes >= static_cast<size_t>(rec) * sizeof(float) * static_cast<size_t>(Ps)) {
-        hipLaunchKernelGGL(gram_slab_kernel, dim3(Ps, (tiles_sym + 7) / 8), dim3(512), 0, st, x, ldx, n_rows, C, sh.MT, ws, rec);
-        if (int rc = dif::launch_status("gram_slab_kernel")) return rc;
+        if (int rc = dif::launch("gram_slab_kernel", gram_slab_kernel, dim3(Ps, (tiles_sym + 7) / 8), dim3(512), 0, st, x, ldx,
+                                 n_rows, C, sh.MT, ws, rec)) return rc;
         return dif::launch_record_finalize(ws, Ps, rec, sh.t_main, tiles_sym, record, st);
     }
     dim3 grid(P, tiles_sym), block(256);
-    if (vec) hipLaunchKernelGGL((simple_reduce_kernel<true, float, true>), grid, block, 0, st, x, ldx, x, ldx, x, ldx, n_rows, sh, ws, rec);
-    else hipLaunchKernelGGL((simple_reduce_kernel<false, float, true>), grid, block, 0, st, x, ldx, x, ldx, x, ldx, n_rows, sh, ws, rec);
-    if (int rc = dif::launch_status("simple_reduce_kernel<sym>")) return rc;
+    if (int rc = dif::with_flags([&](auto VEC) {
+            return dif::launch("simple_reduce_kernel<sym>", simple_reduce_kernel<VEC, float, true>, grid, block, 0, st, x, ldx, x, ldx,
+                               x, ldx, n_rows, sh, ws, rec);
+        }, vec)) return rc;
     return dif::launch_record_finalize(ws, P, rec, sh.t_main, tiles_sym, record, st);
 }
 

@@ -508,18 +508,16 @@ extern "C" int dif_simple_bwd_prep_f32(const float* q, int64_t ldq, const float*
         int64_t Pv = P;
         while ((Pv * 16) % H != 0) --Pv;
         if (Pv < 1) Pv = H;                                  // (H * 16) % H == 0; at most 512 partial records
-        if (M <= 64 && D <= 64)
-            hipLaunchKernelGGL(simple_bwd_prep_vec_kernel<1>, dim3(static_cast<unsigned>(Pv)), dim3(256), 0, st, q, ldq, g, ldg, out,
-                               ldo, reduced, n_rows, static_cast<float>(n_global), H, M, D, gn, gd, part, stride);
-        else
-            hipLaunchKernelGGL(simple_bwd_prep_vec_kernel<2>, dim3(static_cast<unsigned>(Pv)), dim3(256), 0, st, q, ldq, g, ldg, out,
-                               ldo, reduced, n_rows, static_cast<float>(n_global), H, M, D, gn, gd, part, stride);
-        if (int rc = dif::launch_status("simple_bwd_prep_vec_kernel")) return rc;
+        if (int rc = dif::with_flags([&](auto TWO) {              // heads of 65 .. 128 columns: two column blocks per lane
+                return dif::launch("simple_bwd_prep_vec_kernel", simple_bwd_prep_vec_kernel<TWO ? 2 : 1>, dif::grid_of(Pv), dim3(256), 0,
+                                   st, q, ldq, g, ldg, out, ldo, reduced, n_rows, static_cast<float>(n_global), H, M, D, gn, gd, part,
+                                   stride);
+            }, M > 64 || D > 64)) return rc;
         return dif::launch_record_finalize(part, static_cast<int>(Pv), stride, len, -1, sums, st);
     }
-    hipLaunchKernelGGL(simple_bwd_prep_kernel, dim3(static_cast<unsigned>(P)), dim3(256), sizeof(float) * (len + 1), st, q,
-                       ldq, g, ldg, out, ldo, reduced, n_rows, static_cast<float>(n_global), H, M, D, gn, gd, part, stride);
-    if (int rc = dif::launch_status("simple_bwd_prep_kernel")) return rc;
+    if (int rc = dif::launch("simple_bwd_prep_kernel", simple_bwd_prep_kernel, dif::grid_of(P), dim3(256),
+                             sizeof(float) * (len + 1), st, q, ldq, g, ldg, out, ldo, reduced, n_rows, static_cast<float>(n_global),
+                             H, M, D, gn, gd, part, stride)) return rc;
     // column sums of the prep partials -> sums [H*M + 1] (16 slices per column, fixed order)
     return dif::launch_record_finalize(part, static_cast<int>(P), stride, len, -1, sums, st);
 }
@@ -548,29 +546,19 @@ extern "C" int dif_rowgemm_f32(const float* A, int64_t lda, const float* Mat, in
         const int KT = (K + 63) / 64, CT = (C + 63) / 64;
         const size_t lds = static_cast<size_t>(2) * 4 * (2 * KT) * 64 * 16;                  // 16 KiB per 64 channels
         constexpr int kLdsMaxSplit = 2 * 4 * 16 * 64 * 16;
-        static const hipError_t allowed_split = hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_wide_split_kernel),
-                                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMaxSplit);
-        if (allowed_split != hipSuccess)
-            return dif::fail(static_cast<int>(allowed_split), "dif_rowgemm_f32: LDS attribute: %s", hipGetErrorString(allowed_split));
+        if (int rc = dif::allow_lds<&rowgemm_wide_split_kernel>(kLdsMaxSplit, "dif_rowgemm_f32")) return rc;
         int64_t gw = (n_steps + 2 * kRgWaves - 1) / (2 * kRgWaves);
         int64_t cap = (lds <= 80 * 1024 ? 2 : 1) * dif::kCUs / (static_cast<int64_t>(CT) * H);      // one round of workgroups
         if (cap < 1) cap = 1;
         if (gw > cap) gw = cap;
-        hipLaunchKernelGGL(rowgemm_wide_split_kernel, dim3(static_cast<unsigned>(gw), CT, H), dim3(64 * kRgWaves), lds, st, A, lda, K, Mat,
-                           ldm, mat_head_stride, mat_t, mat_scale, bias, r, H, u, u_scale, Cin, ldc, beta_dev, n_rows, K, C, out, ldo);
-        return dif::launch_status("rowgemm_wide_split_kernel");
+        return dif::launch("rowgemm_wide_split_kernel", rowgemm_wide_split_kernel, dif::grid_of(gw, CT, H), dim3(64 * kRgWaves),
+                           lds, st, A, lda, K, Mat, ldm, mat_head_stride, mat_t, mat_scale, bias, r, H, u, u_scale, Cin, ldc,
+                           beta_dev, n_rows, K, C, out, ldo);
     }
     if (K > 64 || C > 64) {
         const int KT = (K + 63) / 64, CT = (C + 63) / 64;
         const size_t lds = static_cast<size_t>(64) * (KT * 64 + 4) * sizeof(float);
         constexpr int kLdsMax = 64 * (8 * 64 + 4) * static_cast<int>(sizeof(float));
-        static const hipError_t allowed[2] = {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_wide_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax),
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_wide_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax)};
-        if (allowed[vec] != hipSuccess)
-            return dif::fail(static_cast<int>(allowed[vec]), "dif_rowgemm_f32: LDS attribute: %s", hipGetErrorString(allowed[vec]));
         int64_t gw = (n_steps + 2 * kRgWaves - 1) / (2 * kRgWaves);          // >= 2 steps per wave: the staging is amortised
         // ONE round of workgroups over the chip, column blocks and heads included: 15,000 x 300 -> 300 (hidden 300 training,
         // image and text/run.sh) was 59 x 5 = 295 workgroups of 82 KB LDS on 256 compute units -- a second round for 39 of them
@@ -579,16 +567,13 @@ extern "C" int dif_rowgemm_f32(const float* A, int64_t lda, const float* Mat, in
         if (cap < 1) cap = 1;
         if (gw > cap) gw = cap;
         const dim3 grid(static_cast<unsigned>(gw), CT, H), block(64 * kRgWaves);
-        if (vec)
-            hipLaunchKernelGGL(rowgemm_wide_kernel<true>, grid, block, lds, st, A, lda, K, Mat, ldm, mat_head_stride, mat_t,
-                               mat_scale, bias, r, H, u, u_scale, Cin, ldc, beta_dev, n_rows, K, C, out, ldo);
-        else
-            hipLaunchKernelGGL(rowgemm_wide_kernel<false>, grid, block, lds, st, A, lda, K, Mat, ldm, mat_head_stride, mat_t,
-                               mat_scale, bias, r, H, u, u_scale, Cin, ldc, beta_dev, n_rows, K, C, out, ldo);
-        return dif::launch_status("rowgemm_wide_kernel");
+        return dif::with_flags([&](auto VEC) -> int {
+            if (int rc = dif::allow_lds<&rowgemm_wide_kernel<VEC>>(kLdsMax, "dif_rowgemm_f32")) return rc;
+            return dif::launch("rowgemm_wide_kernel", rowgemm_wide_kernel<VEC>, grid, block, lds, st, A, lda, K, Mat, ldm,
+                               mat_head_stride, mat_t, mat_scale, bias, r, H, u, u_scale, Cin, ldc, beta_dev, n_rows, K, C, out, ldo);
+        }, vec);
     }
-    hipLaunchKernelGGL(rowgemm_kernel, dim3(static_cast<unsigned>(gx), H), dim3(256), 0, st, A, lda, K, Mat, ldm,
-                       mat_head_stride, mat_t, mat_scale, bias, C, r, H, u, C, u_scale, Cin, ldc, beta_dev, n_rows, K, C, out,
-                       ldo, vec);
-    return dif::launch_status("rowgemm_kernel");
+    return dif::launch("rowgemm_kernel", rowgemm_kernel, dif::grid_of(gx, H), dim3(256), 0, st, A, lda, K, Mat, ldm,
+                       mat_head_stride, mat_t, mat_scale, bias, C, r, H, u, C, u_scale, Cin, ldc, beta_dev, n_rows, K, C, out, ldo,
+                       vec);
 }

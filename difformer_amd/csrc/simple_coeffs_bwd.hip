@@ -254,7 +254,6 @@ extern "C" int dif_simple_coeffs_bwd_f32(const float* record, int64_t n_global, 
     DIF_REQUIRE(C > 0 && C <= 64 && D > 0 && D <= 64, DIF_E_SHAPE, "dif_simple_coeffs_bwd: covers C, D <= 64 (got %d, %d)", C, D);
     DIF_REQUIRE((Wv == nullptr) == (bv == nullptr), DIF_E_BADARG, "dif_simple_coeffs_bwd: Wv and bv go together");
     DIF_REQUIRE(Wv != nullptr || C == D, DIF_E_SHAPE, "dif_simple_coeffs_bwd: without a value projection C must equal D");
-    hipLaunchKernelGGL(coeffs_bwd_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), record,
+    return dif::launch("coeffs_bwd_kernel", coeffs_bwd_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), record,
                        static_cast<float>(n_global), C, D, Wq, bq, Wk, bk, Wv, bv, attn_scale, coef, dcoef, out);
-    return dif::launch_status("coeffs_bwd_kernel");
 }

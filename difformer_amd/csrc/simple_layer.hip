@@ -26,10 +26,7 @@ using dif::bf16x4, dif::bf16x8, dif::cat8, dif::dinv_of, dif::split_bf16, dif::t
 using dif::Elem;
 
 constexpr int kWaves = 4;
-#ifndef DIF_HEAD_WAVES
-#define DIF_HEAD_WAVES 8      // waves per workgroup of the HEAD variant (four 64 x 64 weight blocks in LDS: two workgroups per CU)
-#endif
-constexpr int kHeadWaves = DIF_HEAD_WAVES;
+constexpr int kHeadWaves = 8;           // waves per workgroup of the HEAD variant (four 64 x 64 weight blocks in LDS: two workgroups per CU)
 constexpr int kRecordChunksPerCU = 3;   // partial Gram records per CU that dif_gram_workspace_bytes makes room for
 
 // ------------------------------------------------------------------------------------------------------------
@@ -839,16 +836,14 @@ __device__ __forceinline__ void project_split(f32x4 (&y)[4], const f32x4 (&xa)[4
         }
 }
 
-#ifndef DIF_GATHER_WG
-#define DIF_GATHER_WG 4           // workgroups per CU the GATHER variants are compiled for
-#endif
+constexpr int kGatherWG = 4;            // workgroups per CU the GATHER variants are compiled for
 // SC (single copy): every layer's rows exist ONCE in HBM, as the slice-major pre-scaled copy the sliced product reads.  The
 // kernel then reads its input from that copy (a.x, a.rscale: load_slices) and, between two layers, is launched without a
 // row-major output (a.out null): per layer 34 MB less read and 34 MB less written at 132,534 x 64.  Dense unweighted float32
 // graphs in which every node has an incoming entry (deg > 0: the row is recoverable).  Everything after the load is the same code.
 template <bool EXACT, bool GRAPH_W, typename T = float, bool HEAD = false, bool GATHER = false, bool SPLIT = false, bool SC = false>
 __global__ __launch_bounds__(64 * (HEAD ? kHeadWaves : kWaves),
-                             HEAD ? (2 * kHeadWaves + 3) / 4 : (GATHER ? DIF_GATHER_WG : 4))
+                             HEAD ? (2 * kHeadWaves + 3) / 4 : (GATHER ? kGatherWG : 4))
 void simple_layer_kernel(LayerArgsT<T> a) {
     static_assert(!SPLIT || EXACT, "split-bf16 products: the dense 64 x 64 float32 layers");
     static_assert(!SC || (std::is_same<T, float>::value && !GATHER), "the slice-major copy is float32; it is no gather operand");
@@ -1152,14 +1147,13 @@ int gram_entry(const T* x, int64_t ldx, int64_t n_rows, int C, const int32_t* ro
         if constexpr (std::is_same<T, float>::value) {        // (the slice-major copy is float32-only: no bfloat16 instantiation)
             const int64_t npad = static_cast<int64_t>(plan[6]) * plan[7];
             DIF_REQUIRE(plan[0] == C / 4 && npad >= n_rows, DIF_E_BADARG, "dif_gram: plan does not match C / n_rows");
-            hipLaunchKernelGGL((gram_kernel<true, T>), dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx, n_rows, C, rowptr,
-                               reinterpret_cast<f32x4*>(ys), npad, ws, rec);
+            if (int rc = dif::launch("gram_kernel", gram_kernel<true, T>, dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx, n_rows, C,
+                                     rowptr, reinterpret_cast<f32x4*>(ys), npad, ws, rec)) return rc;
         }
     } else {
-        hipLaunchKernelGGL((gram_kernel<false, T>), dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx, n_rows, C, nullptr, nullptr,
-                           int64_t(0), ws, rec);
+        if (int rc = dif::launch("gram_kernel", gram_kernel<false, T>, dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx, n_rows, C,
+                                 nullptr, nullptr, int64_t(0), ws, rec)) return rc;
     }
-    if (int rc = dif::launch_status("gram_kernel")) return rc;
     return dif::launch_record_finalize(ws, P, rec, C * C + C, 0, record, st);
 }
 }  // namespace
@@ -1195,14 +1189,14 @@ extern "C" int dif_input_gram_f32(const float* x, int64_t ldx, int64_t n_rows, i
     const int64_t rec = (static_cast<int64_t>(D) * D + D + 3) & ~int64_t(3);
     float* ws = static_cast<float*>(workspace);
     const int xvec = (C_in % 4 == 0) && (ldx % 4 == 0) && dif::aligned16(x);
-    const int kq = (C_in + 15) / 16;
-#define DIF_IG2(KQ, ROWS) hipLaunchKernelGGL((input_gram_kernel<KQ, ROWS>), dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx, n_rows, C_in, W, bias, D, \
-                                             ln_weight, ln_bias, ln_eps, relu, out, ldo, rowptr, reinterpret_cast<f32x4*>(ys), npad, ws, rec, xvec)
-#define DIF_IG(KQ) do { if (out) DIF_IG2(KQ, true); else DIF_IG2(KQ, false); } while (0)
-    if (kq == 1) DIF_IG(1); else if (kq == 2) DIF_IG(2); else if (kq == 3) DIF_IG(3); else DIF_IG(4);
-#undef DIF_IG
-#undef DIF_IG2
-    if (int rc = dif::launch_status("input_gram_kernel")) return rc;
+    const int kq = (C_in + 15) / 16;       // 16-column blocks of the input row: 1 .. 4 (C_in <= 64)
+    if (int rc = dif::with_flags([&](auto ROWS) {
+            return dif::with_int<1, 2, 3, 4>(kq, [&](auto KQ) {
+                return dif::launch("input_gram_kernel", input_gram_kernel<KQ, ROWS>, dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx,
+                                   n_rows, C_in, W, bias, D, ln_weight, ln_bias, ln_eps, relu, out, ldo, rowptr,
+                                   reinterpret_cast<f32x4*>(ys), npad, ws, rec, xvec);
+            }, dif::no_variant("dif_input_gram"));
+        }, out != nullptr)) return rc;
     return dif::launch_record_finalize(ws, P, rec, D * D + D, 0, record, st);
 }
 
@@ -1395,14 +1389,9 @@ extern "C" int dif_closed_form_attn_bwd_f32(const float* x, int64_t ldx, int64_t
     const int P = row_chunks(n_rows, sums ? 3 : 4);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool exact = C == 64 && D == 64;
-    if (sums) {
-        if (exact) hipLaunchKernelGGL((closed_form_attn_bwd_kernel<true, true>), dim3(P), dim3(64 * kWaves), 0, st, a);
-        else hipLaunchKernelGGL((closed_form_attn_bwd_kernel<false, true>), dim3(P), dim3(64 * kWaves), 0, st, a);
-    } else {
-        if (exact) hipLaunchKernelGGL((closed_form_attn_bwd_kernel<true, false>), dim3(P), dim3(64 * kWaves), 0, st, a);
-        else hipLaunchKernelGGL((closed_form_attn_bwd_kernel<false, false>), dim3(P), dim3(64 * kWaves), 0, st, a);
-    }
-    return dif::launch_status("closed_form_attn_bwd_kernel");
+    return dif::with_flags([&](auto EXACT, auto SUMS) {
+        return dif::launch("closed_form_attn_bwd_kernel", closed_form_attn_bwd_kernel<EXACT, SUMS>, dim3(P), dim3(64 * kWaves), 0, st, a);
+    }, exact, sums != nullptr);
 }
 
 extern "C" size_t dif_simple_coeffs_len(int C, int D) {
@@ -1417,9 +1406,8 @@ extern "C" int dif_simple_coeffs_f32(const float* record, int64_t n_global, int 
     DIF_REQUIRE(C > 0 && C <= 64 && D > 0 && D <= 64, DIF_E_SHAPE, "dif_simple_coeffs: covers C, D <= 64 (got %d, %d)", C, D);
     DIF_REQUIRE((Wv == nullptr) == (bv == nullptr), DIF_E_BADARG, "dif_simple_coeffs: Wv and bv go together");
     DIF_REQUIRE(Wv != nullptr || C == D, DIF_E_SHAPE, "dif_simple_coeffs: without a value projection C must equal D (difformer.py:120)");
-    hipLaunchKernelGGL(coeffs_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), record,
+    return dif::launch("coeffs_kernel", coeffs_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), record,
                        static_cast<float>(n_global), C, D, Wq, bq, Wk, bk, Wv, bv, attn_scale, coef);
-    return dif::launch_status("coeffs_kernel");
 }
 
 // dif_gram_f32 (no slice-major copy) + dif_simple_coeffs_f32 for one layer input: coef from x in two launches when the Gram
@@ -1442,18 +1430,15 @@ extern "C" int dif_gram_coeffs_f32(const float* x, int64_t ldx, int64_t n_rows, 
     const int64_t rec = (static_cast<int64_t>(C) * C + C + 3) & ~int64_t(3);
     float* ws = static_cast<float*>(workspace);
     DIF_REQUIRE(P <= kFoldedPartsMax || record, DIF_E_BADARG, "dif_gram_coeffs: more than 48 partial records need `record` as the finalize target");
-    hipLaunchKernelGGL((gram_kernel<false, float>), dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx, n_rows, C, nullptr, nullptr,
-                       int64_t(0), ws, rec);
-    if (int rc = dif::launch_status("gram_kernel")) return rc;
+    if (int rc = dif::launch("gram_kernel", gram_kernel<false, float>, dim3(P), dim3(64 * kGramWaves), 0, st, x, ldx, n_rows, C,
+                             nullptr, nullptr, int64_t(0), ws, rec)) return rc;
     if (P <= kFoldedPartsMax) {
-        hipLaunchKernelGGL(coeffs_parts_kernel, dim3(1), dim3(1024), 0, st, ws, P, rec, static_cast<float>(n_global), C, D, Wq, bq, Wk,
-                           bk, Wv, bv, attn_scale, coef, record);
-        return dif::launch_status("coeffs_parts_kernel");
+        return dif::launch("coeffs_parts_kernel", coeffs_parts_kernel, dim3(1), dim3(1024), 0, st, ws, P, rec,
+                           static_cast<float>(n_global), C, D, Wq, bq, Wk, bk, Wv, bv, attn_scale, coef, record);
     }
     if (int rc = dif::launch_record_finalize(ws, P, rec, C * C + C, 0, record, st)) return rc;
-    hipLaunchKernelGGL(coeffs_kernel, dim3(1), dim3(1024), 0, st, record, static_cast<float>(n_global), C, D, Wq, bq, Wk, bk, Wv, bv,
-                       attn_scale, coef);
-    return dif::launch_status("coeffs_kernel");
+    return dif::launch("coeffs_kernel", coeffs_kernel, dim3(1), dim3(1024), 0, st, record, static_cast<float>(n_global), C, D, Wq,
+                       bq, Wk, bk, Wv, bv, attn_scale, coef);
 }
 
 namespace {
@@ -1489,7 +1474,7 @@ int layer_entry(const T* x, int64_t ldx, int64_t n_rows, int C, int D, const flo
     const bool f32 = std::is_same<T, float>::value;
     DIF_REQUIRE(f32 || !next_ys, DIF_E_BADARG, "dif_simple_layer: products for the next layer are float32-only");
     const bool gather = g_rowptr != nullptr;
-    const int P = head ? row_chunks(n_rows, 2, kHeadWaves) : row_chunks(n_rows, gather ? DIF_GATHER_WG : 4);
+    const int P = head ? row_chunks(n_rows, 2, kHeadWaves) : row_chunks(n_rows, gather ? kGatherWG : 4);
     int64_t npad = 0;
     if (next_ys) {
         DIF_REQUIRE(D % 4 == 0, DIF_E_SHAPE, "dif_simple_layer: products for the next layer need D %% 4 == 0");
@@ -1508,43 +1493,24 @@ int layer_entry(const T* x, int64_t ldx, int64_t n_rows, int C, int D, const flo
     const bool gw = (ax != nullptr || gather) && Wv != nullptr;
     // dense 64 x 64 float32 layers (the headline shape): both products on split-bfloat16 operands unless DIFFORMER_EXACT_FP32=1
     const bool split = exact && f32 && !gather && !dif::exact_fp32() &&
-                       (reinterpret_cast<uintptr_t>(coef) & 15u) == 0 && (!gw || (reinterpret_cast<uintptr_t>(Wv) & 15u) == 0);
-    if (sc) {
-        // slice-major input: the split-bf16 kernels at 64 x 64, the general (guarded) kernel for every other shape
-        if constexpr (std::is_same<T, float>::value) {
-#define DIF_LAYER_SC(E, G, H, S) hipLaunchKernelGGL((simple_layer_kernel<E, G, T, H, false, S, true>), dim3(P), dim3(64 * (H ? kHeadWaves : kWaves)), 0, st, a)
-#define DIF_LAYER_SC2(E, S) do { if (head) { if (gw) DIF_LAYER_SC(E, true, true, S); else DIF_LAYER_SC(E, false, true, S); } \
-                                 else { if (gw) DIF_LAYER_SC(E, true, false, S); else DIF_LAYER_SC(E, false, false, S); } } while (0)
-            if (split) DIF_LAYER_SC2(true, true); else DIF_LAYER_SC2(false, false);
-#undef DIF_LAYER_SC2
-#undef DIF_LAYER_SC
-        }
-        return dif::launch_status("simple_layer_kernel");
-    }
-    if (split) {
-        if constexpr (std::is_same<T, float>::value) {
-            if (head) {
-                if (gw) hipLaunchKernelGGL((simple_layer_kernel<true, true, T, true, false, true>), dim3(P), dim3(64 * kHeadWaves), 0, st, a);
-                else hipLaunchKernelGGL((simple_layer_kernel<true, false, T, true, false, true>), dim3(P), dim3(64 * kHeadWaves), 0, st, a);
-            } else {
-                if (gw) hipLaunchKernelGGL((simple_layer_kernel<true, true, T, false, false, true>), dim3(P), dim3(64 * kWaves), 0, st, a);
-                else hipLaunchKernelGGL((simple_layer_kernel<true, false, T, false, false, true>), dim3(P), dim3(64 * kWaves), 0, st, a);
-            }
-            return dif::launch_status("simple_layer_kernel");
-        }
-    }
-#define DIF_LAYER(E, G) hipLaunchKernelGGL((simple_layer_kernel<E, G, T>), dim3(P), dim3(64 * kWaves), 0, st, a)
-#define DIF_LAYER_HEAD(E, G) hipLaunchKernelGGL((simple_layer_kernel<E, G, T, true>), dim3(P), dim3(64 * kHeadWaves), 0, st, a)
-#define DIF_LAYER_GATHER(E, G, H) hipLaunchKernelGGL((simple_layer_kernel<E, G, T, H, true>), dim3(P), dim3(64 * (H ? kHeadWaves : kWaves)), 0, st, a)
-#define DIF_LAYER2(E, G) do { if (gather) { if (head) DIF_LAYER_GATHER(E, G, true); else DIF_LAYER_GATHER(E, G, false); } \
-                              else if (head) DIF_LAYER_HEAD(E, G); else DIF_LAYER(E, G); } while (0)
-    if (exact) { if (gw) DIF_LAYER2(true, true); else DIF_LAYER2(true, false); }
-    else { if (gw) DIF_LAYER2(false, true); else DIF_LAYER2(false, false); }
-#undef DIF_LAYER2
-#undef DIF_LAYER_GATHER
-#undef DIF_LAYER_HEAD
-#undef DIF_LAYER
-    return dif::launch_status("simple_layer_kernel");
+                       dif::aligned<16>(coef) && (!gw || dif::aligned<16>(Wv));
+    // slice-major input: the split-bf16 kernels at 64 x 64, the general (guarded) kernel for every other shape
+    const bool fast = sc ? split : exact;
+    return dif::with_flags([&](auto EXACT, auto GRAPH_W, auto HEAD, auto GATHER, auto SPLIT, auto SC) -> int {
+        // Not built, and never asked for by the conditions above:
+        //   SC with GATHER            the slice-major copy has no in-kernel aggregation (rscale needs !g_rowptr)
+        //   SPLIT with GATHER         the split-bf16 products are the dense 64 x 64 kernels only
+        //   SPLIT without EXACT       split-bf16 operands are staged for full 64 x 64 blocks
+        //   SC with EXACT, no SPLIT   a slice-major layer that is not split runs the general (guarded) kernel
+        //   SC or SPLIT for bfloat16  both read / produce float32 rows
+        if constexpr ((SC && GATHER) || (SPLIT && GATHER) || (SPLIT && !EXACT) || (SC && EXACT && !SPLIT) ||
+                      ((SC || SPLIT) && !std::is_same<T, float>::value))
+            return dif::fail(DIF_E_SHAPE, "dif_simple_layer: no kernel variant <exact %d, graph weight %d, head %d, gather %d, split %d, "
+                             "slice-major %d>", int(EXACT), int(GRAPH_W), int(HEAD), int(GATHER), int(SPLIT), int(SC));
+        else
+            return dif::launch("simple_layer_kernel", simple_layer_kernel<EXACT, GRAPH_W, T, HEAD, GATHER, SPLIT, SC>, dim3(P),
+                               dim3(64 * (HEAD ? kHeadWaves : kWaves)), 0, st, a);
+    }, fast, gw, head, gather, split, sc);
 }
 }  // namespace
 

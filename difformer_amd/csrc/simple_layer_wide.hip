@@ -357,8 +357,8 @@ extern "C" int dif_gram128_f32(const float* x, int64_t ldx, int64_t n_rows, int 
     const int P = gram128_chunks(n_rows);
     const int64_t rec = (static_cast<int64_t>(C) * C + C + 3) & ~int64_t(3);
     float* ws = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(gram128_kernel, dim3(P), dim3(64 * kG128Waves), 0, st, x, ldx, n_rows, C, ws, rec);
-    if (int rc = dif::launch_status("gram128_kernel")) return rc;
+    if (int rc = dif::launch("gram128_kernel", gram128_kernel, dim3(P), dim3(64 * kG128Waves), 0, st, x, ldx, n_rows, C, ws,
+                             rec)) return rc;
     return dif::launch_record_finalize(ws, P, rec, C * C + C, 0, record, st);
 }
 
@@ -388,7 +388,7 @@ extern "C" int dif_simple_layer_wide_f32(const float* x, int64_t ldx, int64_t n_
     const WideArgs a = {x, ldx, bmat, dv, bias, attn_scale, ax, ldax, Wv, bv, row_sums, gcn_scale, x0, ldx0, residual, alpha,
                         ln_weight, ln_bias, ln_eps, relu, out, ldo, n_rows, C, D};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (Wv) hipLaunchKernelGGL((simple_layer_wide_kernel<true>), dim3(static_cast<unsigned>(P)), dim3(64 * kWideWaves), 0, st, a);
-    else hipLaunchKernelGGL((simple_layer_wide_kernel<false>), dim3(static_cast<unsigned>(P)), dim3(64 * kWideWaves), 0, st, a);
-    return dif::launch_status("simple_layer_wide_kernel");
+    return dif::with_flags([&](auto GRAPH_W) {
+        return dif::launch("simple_layer_wide_kernel", simple_layer_wide_kernel<GRAPH_W>, dif::grid_of(P), dim3(64 * kWideWaves), 0, st, a);
+    }, Wv != nullptr);
 }

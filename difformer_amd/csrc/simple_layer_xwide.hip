@@ -276,11 +276,8 @@ XGeo xwide_geometry(int C, int D) {
 template <int KB, int FC>
 int xwide_launch(const XArgs& a, unsigned P, hipStream_t st) {
     constexpr int lds = 2 * KB * 2 * 128 * 16;             // two chunk buffers
-    static const hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void*>(&simple_layer_xwide_kernel<KB, FC>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (he != hipSuccess) return dif::fail(static_cast<int>(he), "dif_simple_layer_xwide: LDS attribute: %s", hipGetErrorString(he));
-    hipLaunchKernelGGL((simple_layer_xwide_kernel<KB, FC>), dim3(P), dim3(64 * kXWaves), lds, st, a);
-    return dif::launch_status("simple_layer_xwide_kernel");
+    if (int rc = dif::allow_lds<&simple_layer_xwide_kernel<KB, FC>>(lds, "dif_simple_layer_xwide")) return rc;
+    return dif::launch("simple_layer_xwide_kernel", simple_layer_xwide_kernel<KB, FC>, dim3(P), dim3(64 * kXWaves), lds, st, a);
 }
 int xwide_dispatch(const XArgs& a, hipStream_t st) {
     const int64_t blocks = (a.n_rows + 16 * kXWaves - 1) / (16 * kXWaves);
@@ -310,9 +307,8 @@ extern "C" int dif_xwide_pack_f32(const float* src, int64_t ld, int transposed, 
                 "dif_xwide_pack: needs src, a 16-byte aligned buffer and C, D <= 416, multiples of 4");
     DIF_REQUIRE(ld >= (transposed ? D : C), DIF_E_BADARG, "dif_xwide_pack: leading dimension smaller than a row");
     const XGeo g = xwide_geometry(C, D);
-    hipLaunchKernelGGL(xwide_pack_kernel, dim3(static_cast<unsigned>((g.kb * g.fc + 1) / 2)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       src, ld, transposed, C, D, g.kb, g.fc, static_cast<bf16x8*>(packed));
-    return dif::launch_status("xwide_pack_kernel");
+    return dif::launch("xwide_pack_kernel", xwide_pack_kernel, dif::grid_of((g.kb * g.fc + 1) / 2), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), src, ld, transposed, C, D, g.kb, g.fc, static_cast<bf16x8*>(packed));
 }
 
 // Closed-form `simple` layer for 128 < max(C, D) <= 416 in one pass (see the head of this file).  packed_m = dif_xwide_pack_f32 of

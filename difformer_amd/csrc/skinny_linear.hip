@@ -900,9 +900,9 @@ int linear_entry(const T* x, int64_t ldx, int64_t n_rows, int C_in, const T* W, 
                 // of this shape is dif_linear_packed_f32, which the host calls with the packed weights it caches.)
                 const int ov = (ldo % 4 == 0) && dif::aligned_v4<T>(out);
                 const unsigned tiles = static_cast<unsigned>((n_rows + 15) / 16);
-                hipLaunchKernelGGL(long_linear_ksplit_exact_kernel, dim3(tiles), dim3(256), 0, static_cast<hipStream_t>(stream), x, ldx,
-                                   n_rows, C_in, W, bias, C_out, ln_weight, ln_bias, ln_eps, relu, out, ldo, ov);
-                return dif::launch_status("long_linear_ksplit_exact_kernel");
+                return dif::launch("long_linear_ksplit_exact_kernel", long_linear_ksplit_exact_kernel, dim3(tiles), dim3(256), 0,
+                                   static_cast<hipStream_t>(stream), x, ldx, n_rows, C_in, W, bias, C_out, ln_weight, ln_bias,
+                                   ln_eps, relu, out, ldo, ov);
             }
         }
         DIF_REQUIRE(C_out <= 64 && C_in <= 8192 && aligned,
@@ -917,21 +917,19 @@ int linear_entry(const T* x, int64_t ldx, int64_t n_rows, int C_in, const T* W, 
             if (!exact && C_in <= 64 * kResidentChunks && n_rows >= 32768) {     // below: the chunked kernel's many small workgroups win
                 const int64_t tiles = (n_rows + 15) / 16;
                 const int64_t wg = (tiles + 15) / 16 < dif::kCUs ? (tiles + 15) / 16 : dif::kCUs;      // one 16-wave workgroup per CU
-                hipLaunchKernelGGL(long_linear_resident_kernel, dim3(static_cast<unsigned>(wg)), dim3(1024), 0,
-                                   static_cast<hipStream_t>(stream), x, ldx, n_rows, C_in, W, bias, C_out, ln_weight, ln_bias, ln_eps,
-                                   relu, out, ldo, ov);
-                return dif::launch_status("long_linear_resident_kernel");
+                return dif::launch("long_linear_resident_kernel", long_linear_resident_kernel, dif::grid_of(wg), dim3(1024), 0,
+                                   static_cast<hipStream_t>(stream), x, ldx, n_rows, C_in, W, bias, C_out, ln_weight, ln_bias,
+                                   ln_eps, relu, out, ldo, ov);
             }
             if (!exact) {
-                hipLaunchKernelGGL(long_linear_split_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0,
-                                   static_cast<hipStream_t>(stream), x, ldx, n_rows, C_in, W, bias, C_out, ln_weight, ln_bias, ln_eps,
-                                   relu, out, ldo, ov);
-                return dif::launch_status("long_linear_split_kernel");
+                return dif::launch("long_linear_split_kernel", long_linear_split_kernel, dif::grid_of(g), dim3(256), 0,
+                                   static_cast<hipStream_t>(stream), x, ldx, n_rows, C_in, W, bias, C_out, ln_weight, ln_bias,
+                                   ln_eps, relu, out, ldo, ov);
             }
         }
-        hipLaunchKernelGGL((long_linear_kernel<T>), dim3(static_cast<unsigned>(g)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
-                           ldx, n_rows, C_in, W, bias, C_out, ln_weight, ln_bias, ln_eps, relu, out, ldo, ov);
-        return dif::launch_status("long_linear_kernel");
+        return dif::launch("long_linear_kernel", long_linear_kernel<T>, dif::grid_of(g), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), x, ldx, n_rows, C_in, W, bias, C_out, ln_weight, ln_bias, ln_eps, relu,
+                           out, ldo, ov);
     }
     DIF_REQUIRE((ln_weight == nullptr) == (ln_bias == nullptr), DIF_E_BADARG,
                 "dif_linear: ln_weight and ln_bias must be given together");
@@ -947,15 +945,11 @@ int linear_entry(const T* x, int64_t ldx, int64_t n_rows, int C_in, const T* W, 
             const int ovec = (ldo % 4 == 0) && dif::aligned_v4<T>(out);
             const int kb = (C_in + 31) / 32;
             hipStream_t st = static_cast<hipStream_t>(stream);
-#define DIF_LINB(KB) \
-            hipLaunchKernelGGL((skinny_linear_bf16_kernel<KB>), dim3(static_cast<unsigned>(gx)), dim3(256), 0, st, x, ldx, n_rows, C_in, W, \
-                               bias, C_out, ln_weight, ln_bias, ln_eps, relu, out, ldo, ovec)
-            if (kb == 1) DIF_LINB(1);
-            else if (kb == 2) DIF_LINB(2);
-            else if (kb == 3) DIF_LINB(3);
-            else DIF_LINB(4);
-#undef DIF_LINB
-            return dif::launch_status("skinny_linear_bf16_kernel");
+            const int kbv = kb < 4 ? kb : 4;                  // 32-column blocks of the input row; the widest kernel takes the rest
+            return dif::with_int<1, 2, 3, 4>(kbv, [&](auto KB) {
+                return dif::launch("skinny_linear_bf16_kernel", skinny_linear_bf16_kernel<KB>, dif::grid_of(gx), dim3(256), 0, st, x, ldx,
+                                   n_rows, C_in, W, bias, C_out, ln_weight, ln_bias, ln_eps, relu, out, ldo, ovec);
+            }, dif::no_variant("dif_linear_bf16"));
         }
     }
     const int kq = (C_in + 15) / 16;
@@ -976,19 +970,11 @@ int linear_entry(const T* x, int64_t ldx, int64_t n_rows, int C_in, const T* W, 
     if (gx < 1) gx = 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
     dim3 grid(static_cast<unsigned>(gx), gy), block(256);
-#define DIF_LIN(KQ) \
-    hipLaunchKernelGGL((skinny_linear_kernel<KQ, T>), grid, block, lds, st, x, ldx, n_rows, C_in, W, bias, C_out, ln_weight, \
-                       ln_bias, ln_eps, relu, out, ldo, vec, ovec, wvec)
-    if (kq == 1) DIF_LIN(1);
-    else if (kq == 2) DIF_LIN(2);
-    else if (kq == 3) DIF_LIN(3);
-    else if (kq == 4) DIF_LIN(4);
-    else if (kq == 5) DIF_LIN(5);
-    else if (kq == 6) DIF_LIN(6);
-    else if (kq == 7) DIF_LIN(7);
-    else DIF_LIN(8);
-#undef DIF_LIN
-    return dif::launch_status("skinny_linear_kernel");
+    const int kqv = kq < 8 ? kq : 8;                          // 16-column blocks of the input row; the widest kernel takes the rest
+    return dif::with_int<1, 2, 3, 4, 5, 6, 7, 8>(kqv, [&](auto KQ) {
+        return dif::launch("skinny_linear_kernel", skinny_linear_kernel<KQ, T>, grid, block, lds, st, x, ldx, n_rows, C_in, W, bias,
+                           C_out, ln_weight, ln_bias, ln_eps, relu, out, ldo, vec, ovec, wvec);
+    }, dif::no_variant("dif_linear"));
 }
 
 }  // namespace
@@ -1007,9 +993,8 @@ extern "C" int dif_linear_pack_f32(const float* W, int C_in, int C_out, void* pa
     DIF_REQUIRE(W && packed && C_in > 0 && C_out > 0 && C_out <= 64, DIF_E_BADARG, "dif_linear_pack_f32: needs W, packed, 0 < C_out <= 64");
     DIF_REQUIRE(dif::aligned16(packed), DIF_E_BADARG, "dif_linear_pack_f32: packed must be 16-byte aligned");
     const int n_chunks = (C_in + 63) / 64;
-    hipLaunchKernelGGL(linear_pack_kernel, dim3(static_cast<unsigned>(n_chunks * 2)), dim3(256), 0, static_cast<hipStream_t>(stream), W,
-                       C_in, C_out, n_chunks, static_cast<bf16x8*>(packed));
-    return dif::launch_status("linear_pack_kernel");
+    return dif::launch("linear_pack_kernel", linear_pack_kernel, dif::grid_of(n_chunks * 2), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), W, C_in, C_out, n_chunks, static_cast<bf16x8*>(packed));
 }
 
 extern "C" int dif_linear_packed_f32(const float* x, int64_t ldx, int64_t n_rows, int C_in, const void* packed, const float* bias,
@@ -1024,11 +1009,10 @@ extern "C" int dif_linear_packed_f32(const float* x, int64_t ldx, int64_t n_rows
     DIF_REQUIRE((n_rows + 15) / 16 < (int64_t(1) << 31), DIF_E_RANGE, "dif_linear_packed_f32: too many rows");
     const int ov = (ldo % 4 == 0) && dif::aligned16(out);
     const int n_chunks = (C_in + 63) / 64;
-    hipLaunchKernelGGL(long_linear_packed_kernel, dim3(static_cast<unsigned>((n_rows + 15) / 16)),
-                       dim3(64 * (n_chunks < kPackedWaves ? n_chunks : kPackedWaves)), 0,
-                       static_cast<hipStream_t>(stream), x, ldx, n_rows, C_in, static_cast<const bf16x8*>(packed), bias, C_out, ln_weight,
-                       ln_bias, ln_eps, relu, out, ldo, ov);
-    return dif::launch_status("long_linear_packed_kernel");
+    return dif::launch("long_linear_packed_kernel", long_linear_packed_kernel, dif::grid_of((n_rows + 15) / 16),
+                       dim3(64 * (n_chunks < kPackedWaves ? n_chunks : kPackedWaves)), 0, static_cast<hipStream_t>(stream), x, ldx,
+                       n_rows, C_in, static_cast<const bf16x8*>(packed), bias, C_out, ln_weight, ln_bias, ln_eps, relu, out, ldo,
+                       ov);
 }
 
 extern "C" int dif_linear_bf16(const void* x, int64_t ldx, int64_t n_rows, int C_in, const void* W, const void* bias,

@@ -924,9 +924,9 @@ extern "C" int dif_tiny_graph_build(const int64_t* edge_index, const float* edge
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st);
     if (e != hipSuccess) return dif::fail(static_cast<int>(e), "dif_tiny_graph_build: memset: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(tiny_graph_kernel, dim3(2), dim3(kGraphThreads), 0, st, edge_index, edge_weight, static_cast<int>(E), static_cast<int>(N),
-                       rowptr, src, val, rowptr_t, dst_t, val_t, status, static_cast<uint32_t*>(workspace));
-    return dif::launch_status("dif_tiny_graph_build");
+    return dif::launch("dif_tiny_graph_build", tiny_graph_kernel, dim3(2), dim3(kGraphThreads), 0, st, edge_index, edge_weight,
+                       static_cast<int>(E), static_cast<int>(N), rowptr, src, val, rowptr_t, dst_t, val_t, status,
+                       static_cast<uint32_t*>(workspace));
 }
 
 extern "C" int dif_tiny_forward_f32(const dif_tiny_cfg* cfg, const float* x, int64_t ldx, const void* const* params,
@@ -943,9 +943,9 @@ extern "C" int dif_tiny_forward_f32(const dif_tiny_cfg* cfg, const float* x, int
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (grid_plan(cfg)) return cfg->kernel == 1 ? grid_sigmoid_forward(a, st) : grid_simple_forward(a, st);
     const int T = block_threads(cfg->n);
-    if (cfg->hidden <= 4) hipLaunchKernelGGL(tiny_forward_kernel<4>, dim3(1), dim3(T), 0, st, a);
-    else hipLaunchKernelGGL(tiny_forward_kernel<8>, dim3(1), dim3(T), 0, st, a);
-    return dif::launch_status("dif_tiny_forward_f32");
+    return dif::with_flags([&](auto NARROW) {               // hidden <= 4: rows padded to 4 columns, 8 otherwise
+        return dif::launch("dif_tiny_forward_f32", tiny_forward_kernel<NARROW ? 4 : 8>, dim3(1), dim3(T), 0, st, a);
+    }, cfg->hidden <= 4);
 }
 
 extern "C" int dif_tiny_backward_f32(const dif_tiny_cfg* cfg, const float* x, int64_t ldx, const void* const* params,
@@ -973,7 +973,7 @@ extern "C" int dif_tiny_backward_f32(const dif_tiny_cfg* cfg, const float* x, in
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (grid_plan(cfg)) return cfg->kernel == 1 ? grid_sigmoid_backward(a, st) : grid_simple_backward(a, st);
     const int T = block_threads(cfg->n);
-    if (cfg->hidden <= 4) hipLaunchKernelGGL(tiny_backward_kernel<4>, dim3(1), dim3(T), 0, st, a);
-    else hipLaunchKernelGGL(tiny_backward_kernel<8>, dim3(1), dim3(T), 0, st, a);
-    return dif::launch_status("dif_tiny_backward_f32");
+    return dif::with_flags([&](auto NARROW) {
+        return dif::launch("dif_tiny_backward_f32", tiny_backward_kernel<NARROW ? 4 : 8>, dim3(1), dim3(T), 0, st, a);
+    }, cfg->hidden <= 4);
 }

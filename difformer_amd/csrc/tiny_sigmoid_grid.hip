@@ -537,26 +537,30 @@ __global__ __launch_bounds__(512) void grid_sums_kernel(const TinyArgs a) {
 template <int DP>
 int forward_launches(const TinyArgs& a, hipStream_t st) {
     const int G = (a.n + kNodes - 1) / kNodes, K = key_splits(a.n);
-    hipLaunchKernelGGL(grid_sigmoid_forward_kernel<DP>, dim3(G), dim3(64), 0, st, a, 0, kFused, 1);
+    const char* what = "dif_tiny_forward_f32";
+    if (int rc = dif::launch(what, grid_sigmoid_forward_kernel<DP>, dim3(G), dim3(64), 0, st, a, 0, kFused, 1)) return rc;
     for (int l = 0; l < a.layers; ++l) {
-        if (K == 1) hipLaunchKernelGGL(grid_sigmoid_forward_kernel<DP>, dim3(G), dim3(kWaves * 64), 0, st, a, l + 1, kFused, 1);
-        else {
-            hipLaunchKernelGGL(grid_sigmoid_forward_kernel<DP>, dim3(G, K), dim3(kWaves * 64), 0, st, a, l + 1, kPairs, K);
-            hipLaunchKernelGGL(grid_sigmoid_forward_kernel<DP>, dim3(G), dim3(64), 0, st, a, l + 1, kTail, K);
+        if (K == 1) {
+            if (int rc = dif::launch(what, grid_sigmoid_forward_kernel<DP>, dim3(G), dim3(kWaves * 64), 0, st, a, l + 1, kFused, 1)) return rc;
+        } else {
+            if (int rc = dif::launch(what, grid_sigmoid_forward_kernel<DP>, dim3(G, K), dim3(kWaves * 64), 0, st, a, l + 1, kPairs, K)) return rc;
+            if (int rc = dif::launch(what, grid_sigmoid_forward_kernel<DP>, dim3(G), dim3(64), 0, st, a, l + 1, kTail, K)) return rc;
         }
     }
-    return dif::launch_status("dif_tiny_forward_f32");
+    return 0;
 }
 
 template <int DP>
 int backward_launches(const TinyArgs& a, hipStream_t st) {
     const int G = (a.n + kNodes - 1) / kNodes, K = key_splits(a.n);
-    hipLaunchKernelGGL(grid_sigmoid_backward_kernel<DP>, dim3(G), dim3(64), 0, st, a, 0, kFused, 1);
+    const char* what = "dif_tiny_backward_f32";
+    if (int rc = dif::launch(what, grid_sigmoid_backward_kernel<DP>, dim3(G), dim3(64), 0, st, a, 0, kFused, 1)) return rc;
     for (int k = 1; k <= a.layers; ++k) {
-        if (K == 1) hipLaunchKernelGGL(grid_sigmoid_backward_kernel<DP>, dim3(G), dim3(kWaves * 64), 0, st, a, k, kFused, 1);
-        else {
-            hipLaunchKernelGGL(grid_sigmoid_backward_kernel<DP>, dim3(G, K), dim3(kWaves * 64), 0, st, a, k, kPairs, K);
-            hipLaunchKernelGGL(grid_sigmoid_backward_kernel<DP>, dim3(G), dim3(64), 0, st, a, k, kTail, K);
+        if (K == 1) {
+            if (int rc = dif::launch(what, grid_sigmoid_backward_kernel<DP>, dim3(G), dim3(kWaves * 64), 0, st, a, k, kFused, 1)) return rc;
+        } else {
+            if (int rc = dif::launch(what, grid_sigmoid_backward_kernel<DP>, dim3(G, K), dim3(kWaves * 64), 0, st, a, k, kPairs, K)) return rc;
+            if (int rc = dif::launch(what, grid_sigmoid_backward_kernel<DP>, dim3(G), dim3(64), 0, st, a, k, kTail, K)) return rc;
         }
     }
     return grid_sums(a, st);
@@ -565,9 +569,10 @@ int backward_launches(const TinyArgs& a, hipStream_t st) {
 }  // namespace
 
 int tiny::grid_sums(const TinyArgs& a, hipStream_t st) {
-    if (a.d <= 4) hipLaunchKernelGGL(grid_sums_kernel<4>, dim3(a.c + 1 + 8 * a.layers + 3 + a.d), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL(grid_sums_kernel<8>, dim3(a.c + 1 + 8 * a.layers + 3 + a.d), dim3(512), 0, st, a);
-    return dif::launch_status("dif_tiny_backward_f32");
+    return dif::with_flags([&](auto NARROW) {               // d <= 4: rows padded to 4 columns, 8 otherwise
+        return dif::launch("dif_tiny_backward_f32", grid_sums_kernel<NARROW ? 4 : 8>, dim3(a.c + 1 + 8 * a.layers + 3 + a.d), dim3(512),
+                           0, st, a);
+    }, a.d <= 4);
 }
 
 int tiny::grid_sigmoid_forward(const TinyArgs& a, hipStream_t st) {

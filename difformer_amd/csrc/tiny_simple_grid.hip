@@ -425,15 +425,16 @@ __global__ __launch_bounds__(kThreads) void grid_simple_backward_kernel(const Ti
 template <int DP>
 int forward_launches(const TinyArgs& a, hipStream_t st) {
     const int G = (a.n + kNodes - 1) / kNodes;
-    for (int s = 0; s <= a.layers; ++s) hipLaunchKernelGGL(grid_simple_forward_kernel<DP>, dim3(G), dim3(kThreads), 0, st, a, s);
-    return dif::launch_status("dif_tiny_forward_f32");
+    for (int s = 0; s <= a.layers; ++s)
+        if (int rc = dif::launch("dif_tiny_forward_f32", grid_simple_forward_kernel<DP>, dim3(G), dim3(kThreads), 0, st, a, s)) return rc;
+    return 0;
 }
 
 template <int DP>
 int backward_launches(const TinyArgs& a, hipStream_t st) {
     const int G = (a.n + kNodes - 1) / kNodes;
-    for (int s = 0; s <= a.layers; ++s) hipLaunchKernelGGL(grid_simple_backward_kernel<DP>, dim3(G), dim3(kThreads), 0, st, a, s);
-    if (int rc = dif::launch_status("dif_tiny_backward_f32")) return rc;
+    for (int s = 0; s <= a.layers; ++s)
+        if (int rc = dif::launch("dif_tiny_backward_f32", grid_simple_backward_kernel<DP>, dim3(G), dim3(kThreads), 0, st, a, s)) return rc;
     return grid_sums(a, st);
 }
 

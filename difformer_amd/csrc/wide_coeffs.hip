@@ -118,9 +118,8 @@ extern "C" int dif_wide_coeffs_f64(const float* record, int C, int64_t n_global,
     DIF_REQUIRE(C1 <= 513, DIF_E_SHAPE, "dif_wide_coeffs: C <= 512 (got %d)", C);
     const int gy = (C1 + kWT - 1) / kWT, gx = (DV + kWT - 1) / kWT;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(wide_gemm_kernel<0>, dim3(gx, gy), dim3(64 * kWWaves), 0, st, record, C, static_cast<double>(n_global), S, nullptr, V, DV, T,
-                       partial, gy, nullptr, nullptr);
-    if (int rc = dif::launch_status("wide_gemm_kernel<0>")) return rc;
-    hipLaunchKernelGGL(wide_gemm_kernel<1>, dim3(gx, gy), dim3(64 * kWWaves), 0, st, nullptr, C, 0.0, nullptr, P, T, DV, T, partial, gy, B, bias);
-    return dif::launch_status("wide_gemm_kernel<1>");
+    if (int rc = dif::launch("wide_gemm_kernel<0>", wide_gemm_kernel<0>, dim3(gx, gy), dim3(64 * kWWaves), 0, st, record, C,
+                             static_cast<double>(n_global), S, nullptr, V, DV, T, partial, gy, nullptr, nullptr)) return rc;
+    return dif::launch("wide_gemm_kernel<1>", wide_gemm_kernel<1>, dim3(gx, gy), dim3(64 * kWWaves), 0, st, nullptr, C, 0.0,
+                       nullptr, P, T, DV, T, partial, gy, B, bias);
 }

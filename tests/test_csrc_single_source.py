@@ -1,4 +1,5 @@
-"""The split-bf16 contract and the shared tile helpers are written once: csrc/split_bf16.h and csrc/dif_common.h.
+"""The split-bf16 contract and the shared tile helpers are written once: csrc/split_bf16.h and csrc/dif_common.h.  So is the
+host side of a launch: csrc/dif_launch.h (launch + status, the dynamic-LDS attribute) and csrc/dif_select.h (variant selectors).
 Reads the device sources as text (no compiler, no GPU) so that the per-file copies cannot grow back."""
 import os
 import re
@@ -65,8 +66,44 @@ def test_every_shared_helper_is_defined_exactly_once():
 def test_the_radix_pass_kernels_are_launched_from_one_place():
     """csrc/gcn_csr.hip: every sort of the graph construction goes through the one pass loop."""
     text = sources()["gcn_csr.hip"]
-    assert text.count("hipLaunchKernelGGL(radix_hist_kernel") == 1
-    assert text.count("hipLaunchKernelGGL(radix_scatter_kernel") == 1
+    assert text.count('dif::launch("radix_hist_kernel", radix_hist_kernel,') == 1
+    assert text.count('dif::launch("radix_scatter_kernel", radix_scatter_kernel,') == 1
+    assert len(re.findall(r"\bradix_hist_kernel\s*,", text)) == 1 and len(re.findall(r"\bradix_scatter_kernel\s*,", text)) == 1
+
+
+LAUNCH_HOME = "dif_launch.h"
+SIDE_LIBRARIES = ("attn_topk.hip", "attn_edges.hip")      # their own shared objects, their own last-error text
+LAUNCH = re.compile(r"\bhipLaunchKernelGGL\b|<<<|\bdif::launch\s*\(|\bhipLaunchKernel\b|\bhipModuleLaunchKernel\b")
+
+
+def function_like_macros(text):
+    """[(name, body)] of every `#define NAME(...) body`, continuation lines joined"""
+    return [(m.group(1), m.group(2).replace("\\\n", " "))
+            for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)\([^)]*\)((?:[^\n\\]|\\\n|\\.)*)", text, flags=re.M)]
+
+
+def test_no_macro_expands_to_a_kernel_launch():
+    """A launcher turns run-time facts into template arguments with dif::with_flags / dif::with_int, not with a private macro."""
+    offenders = {(n, name) for n, t in sources().items() for name, body in function_like_macros(t) if LAUNCH.search(body)}
+    assert not offenders, offenders
+
+
+def test_the_lds_attribute_is_set_in_one_place():
+    assert [n for n, t in sources().items() if "hipFuncSetAttribute" in t] == [LAUNCH_HOME]
+
+
+def test_kernels_are_launched_through_the_launch_helper():
+    """libdifformer_hip.so: dif::launch only.  The two side libraries keep their own status check and launch directly."""
+    users = sorted(n for n, t in sources().items() if "hipLaunchKernelGGL" in t or "<<<" in t)
+    assert users == sorted((LAUNCH_HOME,) + SIDE_LIBRARIES), users
+    assert sources()[LAUNCH_HOME].count("hipLaunchKernelGGL(") == 1
+
+
+def test_the_macro_finder_sees_a_launch_macro():
+    text = "#define DIF_X(G, V)  \\\n    do { \\\n        hipLaunchKernelGGL((k<G, V>), grid, block, 0, st, a); \\\n    } while (0)\n#define DIF_Y(c) ((c) + 1)\n"
+    found = dict(function_like_macros(text))
+    assert set(found) == {"DIF_X", "DIF_Y"} and LAUNCH.search(found["DIF_X"]) and not LAUNCH.search(found["DIF_Y"])
+    assert LAUNCH.search("return dif::launch(\"k\", k<G>, grid, block, 0, st);") and LAUNCH.search("k<<<g, b, 0, st>>>(a);")
 
 
 def test_the_sort_rounds_formula_is_written_once():
