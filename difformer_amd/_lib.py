@@ -19,6 +19,9 @@ MAPS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "diffor
 # the edge-attention library (C ABI: include/difformer_edges.h), loaded on first use by load_edges()
 EDGES_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_edges.so")
 EDGES_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_edges.h"))
+# the k-nearest-neighbour graph library (C ABI: include/difformer_knn.h), loaded on first use by load_knn()
+KNN_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_knn.so")
+KNN_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_knn.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -125,9 +128,15 @@ _edges_code = _read_header(EDGES_HEADER_PATH)
 EDGES_VERSION = _defines(_edges_code, "DIF_EDGES_VERSION")["DIF_EDGES_VERSION"]
 EDGES_SIGNATURES = _prototypes(_edges_code)
 
+# ... and include/difformer_knn.h of the fourth's
+_knn_code = _read_header(KNN_HEADER_PATH)
+KNN_VERSION = _defines(_knn_code, "DIF_KNN_VERSION")["DIF_KNN_VERSION"]
+KNN_SIGNATURES = _prototypes(_knn_code)
+
 _lib = None
 _maps = None
 _edges = None
+_knn = None
 
 
 class DifformerHipError(RuntimeError):
@@ -214,6 +223,14 @@ def load_edges():
     return _edges
 
 
+def load_knn():
+    """Load libdifformer_knn.so once."""
+    global _knn
+    if _knn is None:
+        _knn = _load_side(KNN_LIB_PATH, KNN_SIGNATURES, "dif_knn_version", KNN_VERSION)
+    return _knn
+
+
 def check_maps(rc, what):
     """check() for a call into libdifformer_maps.so: the message comes from that library."""
     if rc != 0:
@@ -225,6 +242,13 @@ def check_edges(rc, what):
     """check() for a call into libdifformer_edges.so: the message comes from that library."""
     if rc != 0:
         msg = load_edges().dif_edges_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
+
+
+def check_knn(rc, what):
+    """check() for a call into libdifformer_knn.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_knn().dif_knn_last_error()
         raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 

@@ -219,14 +219,16 @@ class HipBackend:
         torch.cuda.synchronize()
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
-    def _call(self, label, symbol, dev, *args, maps=False, edges=False):
+    def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False):
         """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
         a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
         `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
-        collection, operands on the current device -- adds nothing around the call.  maps / edges: `symbol` is one of
-        libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so (include/difformer_edges.h), loaded on
-        first use."""
-        fn = getattr(_lib.load_maps() if maps else (_lib.load_edges() if edges else self.lib), symbol)
+        collection, operands on the current device -- adds nothing around the call.  maps / edges / knn: `symbol` is one of
+        libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so (include/difformer_edges.h) /
+        libdifformer_knn.so (include/difformer_knn.h), loaded on first use."""
+        side = (_lib.load_maps, _lib.check_maps) if maps else ((_lib.load_edges, _lib.check_edges) if edges else
+                                                               ((_lib.load_knn, _lib.check_knn) if knn else None))
+        fn = getattr(side[0]() if side else self.lib, symbol)
         index = dev.index
         if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
             rc = fn(*args, _raw_stream(index) if _raw_stream is not None else _stream(dev))
@@ -234,7 +236,7 @@ class HipBackend:
             with _Timed(self, label, dev):
                 rc = fn(*args, _stream(dev))
         if rc != 0:
-            (_lib.check_maps if maps else (_lib.check_edges if edges else _lib.check))(rc, symbol)
+            (side[1] if side else _lib.check)(rc, symbol)
 
     # ---- a1 --------------------------------------------------------------------------------
     def simple_reduce(self, q, k, v):
@@ -384,6 +386,31 @@ class HipBackend:
         self._call("dif_attn_topk_f32", "dif_attn_topk_f32", dev, _ptr(q), ldq, _ptr(k), ldk, N, L, H, M, int(mode), int(topk),
                    _ptr(values), _ptr(indices), _ptr(ws), ws_bytes, maps=True)
         return values, indices
+
+    # ---- k-nearest-neighbour graphs (libdifformer_knn.so) -----------------------------------------
+    def knn_graph(self, x, k, loop, metric, centre_row, want_dist=False, route=-1):
+        """x [N,M] float32, M a multiple of 4 up to 512, 1 <= k <= 24 -> (edge_index int64 [2, N kk], dist float32 [N kk] or
+        None), kk = min(k, N - (0 if loop else 1)): per row its kk nearest rows, nearest first, ranked by float64 distances
+        (metric 0: squared Euclidean, 1: cosine), ties to the lower index; row `centre_row` of edge_index holds the row
+        itself, the other its neighbours.  route: -1 (automatic), 0 (direct, M <= 16), 1 (sweep).  No [N, N] tensor exists
+        (csrc/knn_graph.hip).  x is taken as it is: rows of unit column stride that start on 16-byte boundaries (the caller,
+        neighbors.py, copies any other view)."""
+        dev = _require_device(x)
+        _all_f32(x=x)
+        N, M = x.shape
+        ldx = int(x.stride(0)) if N > 1 else M
+        if x.stride(1) != 1 or ldx < M or ldx % 4 or x.data_ptr() % 16:
+            raise ValueError("difformer_amd: knn_graph takes rows of unit column stride on 16-byte boundaries "
+                             f"(got strides {tuple(x.stride())}, address % 16 = {x.data_ptr() % 16})")
+        knn = _lib.load_knn()
+        kk = min(int(k), N - (0 if loop else 1))
+        edge_index = torch.empty((2, N * kk), dtype=torch.int64, device=dev)
+        dist = torch.empty(N * kk, dtype=torch.float32, device=dev) if want_dist else None
+        ws_bytes = knn.dif_knn_workspace_bytes(N, M, int(k), int(bool(loop)), int(metric), int(route))
+        ws = _workspace(ws_bytes, dev, floor=16)
+        self._call("dif_knn_graph_f32", "dif_knn_graph_f32", dev, _ptr(x), ldx, N, M, int(k), int(bool(loop)), int(metric),
+                   int(centre_row), int(route), _ptr(edge_index), _ptr(dist), _ptr(ws), ws_bytes, knn=True)
+        return edge_index, dist
 
     # ---- attention on graph edges (libdifformer_edges.so) ----------------------------------------
     def edge_attention(self, q, k, scale, edge_index, mode):
