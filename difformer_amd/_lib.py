@@ -22,6 +22,9 @@ EDGES_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "diffo
 # the k-nearest-neighbour graph library (C ABI: include/difformer_knn.h), loaded on first use by load_knn()
 KNN_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_knn.so")
 KNN_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_knn.h"))
+# the slot-order library of the packed sliced schedule (C ABI: include/difformer_slots.h), loaded on first use by load_slots()
+SLOTS_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_slots.so")
+SLOTS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_slots.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -133,10 +136,16 @@ _knn_code = _read_header(KNN_HEADER_PATH)
 KNN_VERSION = _defines(_knn_code, "DIF_KNN_VERSION")["DIF_KNN_VERSION"]
 KNN_SIGNATURES = _prototypes(_knn_code)
 
+# ... and include/difformer_slots.h of the fifth's
+_slots_code = _read_header(SLOTS_HEADER_PATH)
+SLOTS_VERSION = _defines(_slots_code, "DIF_SLOTS_VERSION")["DIF_SLOTS_VERSION"]
+SLOTS_SIGNATURES = _prototypes(_slots_code)
+
 _lib = None
 _maps = None
 _edges = None
 _knn = None
+_slots = None
 
 
 class DifformerHipError(RuntimeError):
@@ -231,6 +240,14 @@ def load_knn():
     return _knn
 
 
+def load_slots():
+    """Load libdifformer_slots.so once."""
+    global _slots
+    if _slots is None:
+        _slots = _load_side(SLOTS_LIB_PATH, SLOTS_SIGNATURES, "dif_slots_version", SLOTS_VERSION)
+    return _slots
+
+
 def check_maps(rc, what):
     """check() for a call into libdifformer_maps.so: the message comes from that library."""
     if rc != 0:
@@ -249,6 +266,13 @@ def check_knn(rc, what):
     """check() for a call into libdifformer_knn.so: the message comes from that library."""
     if rc != 0:
         msg = load_knn().dif_knn_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
+
+
+def check_slots(rc, what):
+    """check() for a call into libdifformer_slots.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_slots().dif_slots_last_error()
         raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 

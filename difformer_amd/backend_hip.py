@@ -219,15 +219,17 @@ class HipBackend:
         torch.cuda.synchronize()
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
-    def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False):
+    def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False, slots=False):
         """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
         a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
         `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
-        collection, operands on the current device -- adds nothing around the call.  maps / edges / knn: `symbol` is one of
-        libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so (include/difformer_edges.h) /
-        libdifformer_knn.so (include/difformer_knn.h), loaded on first use."""
+        collection, operands on the current device -- adds nothing around the call.  maps / edges / knn / slots: `symbol` is
+        one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so (include/difformer_edges.h) /
+        libdifformer_knn.so (include/difformer_knn.h) / libdifformer_slots.so (include/difformer_slots.h), loaded on first
+        use."""
         side = (_lib.load_maps, _lib.check_maps) if maps else ((_lib.load_edges, _lib.check_edges) if edges else
-                                                               ((_lib.load_knn, _lib.check_knn) if knn else None))
+                                                               ((_lib.load_knn, _lib.check_knn) if knn else
+                                                                ((_lib.load_slots, _lib.check_slots) if slots else None)))
         fn = getattr(side[0]() if side else self.lib, symbol)
         index = dev.index
         if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
@@ -999,6 +1001,22 @@ class HipBackend:
                    int(n_rows), int(F), plan, _ptr(order), _ptr(parts), n_pos, _ptr(srt), _ptr(counts), _ptr(table),
                    max(n_blocks, 1), _ptr(entries))
         return entries, table
+
+    def sliced_slot_order(self, rowptr, blkptr, n_src, row_begin, n_rows, plan):
+        """Rows of the shard in the dealt order of the packed schedule (csrc/sliced_slots.hip, include/difformer_slots.h):
+        int32 [n_rows] on the device, no host sync -- or None for a geometry the call does not cover (more than 18 tiles,
+        or (panel, wave) pairs x tiles beyond the deal's LDS) or when libdifformer_slots.so is not there."""
+        if not os.path.exists(_lib.SLOTS_LIB_PATH):
+            return None
+        dev = _require_device(rowptr, blkptr)
+        ws_bytes = _lib.load_slots().dif_sliced_slot_order_workspace_bytes(int(n_rows), plan)
+        if ws_bytes <= 0:
+            return None
+        order = torch.empty(int(n_rows), dtype=torch.int32, device=dev)
+        ws = _workspace(ws_bytes, dev)
+        self._call("dif_sliced_slot_order", "dif_sliced_slot_order", dev, _ptr(rowptr), _ptr(blkptr), int(n_src), int(row_begin),
+                   int(n_rows), plan, _ptr(order), _ptr(ws), ws_bytes, slots=True)
+        return order
 
     def sliced_prescale(self, x, rowptr, n_src, plan, dinv=None):
         """x [n_src, F] fp32 -> ys [F/4, T*NT, 4]: rows scaled by deg^-1/2 (dinv, or from the row lengths), slice-major."""

@@ -22,6 +22,9 @@
 
 namespace {
 
+// ---- the device sort and what it rests on (scan, radix passes, workspace layout).  csrc/sliced_slots.hip, a library of
+// its own, includes this file with DIF_GCN_CSR_SORT_ONLY defined and gets this part alone: one home for the sort, a copy of
+// its kernels in either shared object -----------------------------------------------------------------------------------
 constexpr int kScanBlock = 256;
 constexpr int kScanItems = 4;
 constexpr int kScanTile = kScanBlock * kScanItems;  // 1024 values per block
@@ -31,48 +34,6 @@ constexpr int kSortRoundsMax = 64;  // 64 lanes x 64 rounds = 4096 keys per wave
 constexpr int kSortRoundsMin = 8;   // small graphs (mini-batches): shorter chunks so that >= ~1000 waves share the sort
 constexpr int kRadixBits = 8;
 constexpr int kRadix = 1 << kRadixBits;
-
-// ---- sort keys (row it is filed under x source block) and payloads --------------------------------
-// Payload: the edge id when the graph is weighted (the weight is fetched after the sort), otherwise directly the node
-// id the entry will gather -- the sorted payload then IS the CSR `src` array and the fill pass needs no random access
-// into edge_index.  No per-key counting here: the pointer table is read off the sorted keys (csr_bounds_kernel).
-__global__ __launch_bounds__(256) void csr_count_kernel(const int64_t* __restrict__ edge_index, int64_t E,
-                                                        int64_t N, int64_t NB, int64_t block_rows, int transpose,
-                                                        int weighted, uint32_t* __restrict__ keys,
-                                                        uint32_t* __restrict__ vals, int32_t* __restrict__ degc,
-                                                        int32_t* __restrict__ status) {
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < E; e += stride) {
-        int64_t r = edge_index[e];             // source       (row, difformer.py:65)
-        int64_t c = edge_index[E + e];         // destination  (col)
-        if (r < 0 || r >= N || c < 0 || c >= N) {
-            atomicOr(status, 1);
-            r = 0; c = 0;  // keep the build memory-safe; the host rejects the result
-        }
-        // forward: entries grouped by destination (col), blocked by source; transposed (backward of the aggregation):
-        // grouped by source (row), blocked by destination
-        // node ids are < 2^31 here (range check above) and the key fits 32 bits (checked by the host): 32-bit arithmetic --
-        // a 64-bit integer division per edge made this pass 1.7 ms at C4 (1.1 TB/s for a streaming kernel)
-        const uint32_t ru = static_cast<uint32_t>(r), cu = static_cast<uint32_t>(c), br = static_cast<uint32_t>(block_rows),
-                       nb = static_cast<uint32_t>(NB);
-        const uint32_t key = transpose ? ru * nb + cu / br : cu * nb + ru / br;
-        keys[e] = key;
-        vals[e] = weighted ? static_cast<uint32_t>(e) : static_cast<uint32_t>(transpose ? c : r);
-        if (transpose) atomicAdd(&degc[c], 1); // the normalisation always uses the in-degree over `col` (:66)
-    }
-}
-
-// kptr[j] = first position of the sorted keys holding a key >= j, for j in [0, n_keys]  (kptr[n_keys] = E): thread k
-// owns the gap between key[k-1] and key[k].  Replaces E atomic increments + a scan over the n_keys counters.
-__global__ __launch_bounds__(256) void csr_bounds_kernel(const uint32_t* __restrict__ key_sorted, int64_t E,
-                                                         int64_t n_keys, int32_t* __restrict__ kptr) {
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    for (int64_t k = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; k <= E; k += stride) {
-        const int64_t lo = (k == 0) ? 0 : static_cast<int64_t>(key_sorted[k - 1]) + 1;
-        const int64_t hi = (k == E) ? n_keys : static_cast<int64_t>(key_sorted[k]);
-        for (int64_t j = lo; j <= hi; ++j) kptr[j] = static_cast<int32_t>(k);
-    }
-}
 
 // ---- device-wide exclusive scan of int32 (3 phases) -----------------------------------------
 __global__ __launch_bounds__(kScanBlock) void scan_block_sums_kernel(const int32_t* __restrict__ in, int64_t n,
@@ -161,33 +122,6 @@ int exclusive_scan(const int32_t* in, int64_t n, int32_t* out, int32_t* out_tota
     if (int rc = dif::launch("exclusive_scan", scan_of_sums_kernel, dim3(1), dim3(1024), 0, st, bsum, nb)) return rc;
     return dif::launch("exclusive_scan", scan_apply_kernel, dif::grid_of(nb), dim3(kScanBlock), 0, st, in, n, bsum, nb, out,
                        out_total);
-}
-
-// From the key pointers kptr[dst*NB + blk]: rowptr, block-major blkptr, and
-// dinv[n] = sqrt(1/deg[n])  (float32, correctly rounded: difformer.py:67-68); deg 0 -> inf
-__global__ __launch_bounds__(256) void csr_ptrs_kernel(const int32_t* __restrict__ kptr, int64_t N, int64_t NB,
-                                                       int32_t* __restrict__ rowptr, int32_t* __restrict__ blkptr,
-                                                       const int32_t* __restrict__ degc, float* __restrict__ dinv,
-                                                       int32_t* __restrict__ longest) {
-    const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    int32_t len = 0;
-    if (r <= N) {
-        const int32_t start = kptr[r * NB];
-        rowptr[r] = start;                         // r == N: kptr[N*NB] = E
-        if (r < N) {
-            const int32_t end = kptr[(r + 1) * NB];
-            len = end - start;
-            dinv[r] = sqrtf(1.0f / static_cast<float>(degc ? degc[r] : end - start));
-            if (blkptr) {
-                for (int64_t b = 0; b < NB; ++b) blkptr[b * N + r] = kptr[r * NB + b];
-                blkptr[NB * N + r] = end;
-            }
-        }
-    }
-    // the longest row of the CSR (status[1]): one atomic per wave
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const int32_t o = __shfl_xor(len, off, 64); len = o > len ? o : len; }
-    if ((threadIdx.x & 63) == 0 && len > 0) atomicMax(longest, len);
 }
 
 // ---- stable LSD radix sort, 8 bits per pass; each WAVE owns a 4096-key chunk -------------------
@@ -292,6 +226,163 @@ __global__ __launch_bounds__(64 * kSortWaves) void radix_scatter_kernel(
         keys_out[dst] = key;
         vals_out[dst] = val;
     }
+}
+
+int zero_async(const char* who, void* p, size_t bytes, hipStream_t st) {
+    const hipError_t he = hipMemsetAsync(p, 0, bytes, st);
+    return he == hipSuccess ? 0 : dif::fail(static_cast<int>(he), "%s: memset: %s", who, hipGetErrorString(he));
+}
+
+int check_workspace(const char* who, const void* workspace, size_t have, size_t need) {
+    DIF_REQUIRE(have >= need, DIF_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, have, need);
+    DIF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, DIF_E_BADARG, "%s: workspace must be 256-byte aligned", who);
+    return 0;
+}
+
+// ---- workspace layout: 256-byte aligned pieces, one after the other --------------------------------------------------
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+struct Arena {
+    size_t o = 0;                                   // bytes taken so far = the total when the layout is complete
+    size_t take(size_t bytes) { const size_t at = o; o += align256(bytes); return at; }
+};
+
+// block sums of exclusive_scan over scan_n values (+ 1: the grand total)
+inline size_t scan_scratch_bytes(int64_t scan_n) { return static_cast<size_t>((scan_n + kScanTile - 1) / kScanTile + 1) * 4; }
+
+template <class T> T* at(char* ws, size_t off) { return reinterpret_cast<T*>(ws + off); }
+template <class T> const T* at(const char* ws, size_t off) { return reinterpret_cast<const T*>(ws + off); }
+
+// ---- the sort: geometry, buffers, the pass loop ----------------------------------------------------------------------
+struct SortGeom {
+    int64_t n;             // (key, payload) pairs
+    int rounds;            // 64-key rounds per wave chunk
+    int64_t n_chunks;      // sort chunks (waves)
+    int64_t table_len;     // kRadix * n_chunks
+    int passes;            // radix passes, kRadixBits of the key each
+};
+
+// passes that order keys in [0, n_keys)
+int key_passes(int64_t n_keys) {
+    int bits = 1;
+    while ((int64_t(1) << bits) < n_keys) ++bits;
+    return (bits + kRadixBits - 1) / kRadixBits;
+}
+
+// rounds = 0: from the item count
+SortGeom sort_geom(int64_t n, int passes, int64_t rounds = 0) {
+    SortGeom g;
+    g.n = n;
+    constexpr int64_t per_round = 64 * 4096;                         // aim at ~4096 waves
+    if (rounds == 0) rounds = (n + per_round - 1) / per_round;
+    if (rounds < kSortRoundsMin) rounds = kSortRoundsMin;
+    if (rounds > kSortRoundsMax) rounds = kSortRoundsMax;
+    g.rounds = static_cast<int>(rounds);
+    const int64_t chunk = 64 * rounds;
+    g.n_chunks = (n + chunk - 1) / chunk;
+    if (g.n_chunks < 1) g.n_chunks = 1;
+    g.table_len = g.n_chunks * kRadix;
+    g.passes = passes;
+    return g;
+}
+
+struct SortBufs {
+    uint32_t *kin, *kout;    // keys: what the next pass reads, what it writes
+    uint32_t *vin, *vout;    // payload, likewise
+    int32_t *table, *bsum;   // per-chunk digit counts [table_len] and the scratch of their scan
+};
+
+// g.passes stable passes over the pairs in (b.kin, b.vin), lowest digit first.  Every pass swaps the roles of the two pairs
+// of buffers, so on return b.kin / b.vin hold the sorted keys / payload wherever the last pass left them: in the pair that
+// came in as (kout, vout) after an odd number of passes, in the one that came in as (kin, vin) after an even number.
+int radix_sort(const SortGeom& g, SortBufs& b, hipStream_t st) {
+    const unsigned sort_grid = static_cast<unsigned>((g.n_chunks + kSortWaves - 1) / kSortWaves);
+    for (int pass = 0; pass < g.passes; ++pass) {
+        const int shift = pass * kRadixBits;
+        if (int rc = dif::launch("radix_hist_kernel", radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin, g.n,
+                                 shift, g.n_chunks, g.rounds, b.table)) return rc;
+        if (int rc = exclusive_scan(b.table, g.table_len, b.table, nullptr, b.bsum, st)) return rc;
+        if (int rc = dif::launch("radix_scatter_kernel", radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin,
+                                 b.vin, g.n, shift, g.n_chunks, g.rounds, b.table, b.kout, b.vout)) return rc;
+        uint32_t* t = b.kin; b.kin = b.kout; b.kout = t;
+        t = b.vin; b.vin = b.vout; b.vout = t;
+    }
+    return 0;
+}
+
+}  // namespace
+
+#ifndef DIF_GCN_CSR_SORT_ONLY
+
+namespace {
+
+// ---- sort keys (row it is filed under x source block) and payloads --------------------------------
+// Payload: the edge id when the graph is weighted (the weight is fetched after the sort), otherwise directly the node
+// id the entry will gather -- the sorted payload then IS the CSR `src` array and the fill pass needs no random access
+// into edge_index.  No per-key counting here: the pointer table is read off the sorted keys (csr_bounds_kernel).
+__global__ __launch_bounds__(256) void csr_count_kernel(const int64_t* __restrict__ edge_index, int64_t E,
+                                                        int64_t N, int64_t NB, int64_t block_rows, int transpose,
+                                                        int weighted, uint32_t* __restrict__ keys,
+                                                        uint32_t* __restrict__ vals, int32_t* __restrict__ degc,
+                                                        int32_t* __restrict__ status) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < E; e += stride) {
+        int64_t r = edge_index[e];             // source       (row, difformer.py:65)
+        int64_t c = edge_index[E + e];         // destination  (col)
+        if (r < 0 || r >= N || c < 0 || c >= N) {
+            atomicOr(status, 1);
+            r = 0; c = 0;  // keep the build memory-safe; the host rejects the result
+        }
+        // forward: entries grouped by destination (col), blocked by source; transposed (backward of the aggregation):
+        // grouped by source (row), blocked by destination
+        // node ids are < 2^31 here (range check above) and the key fits 32 bits (checked by the host): 32-bit arithmetic --
+        // a 64-bit integer division per edge made this pass 1.7 ms at C4 (1.1 TB/s for a streaming kernel)
+        const uint32_t ru = static_cast<uint32_t>(r), cu = static_cast<uint32_t>(c), br = static_cast<uint32_t>(block_rows),
+                       nb = static_cast<uint32_t>(NB);
+        const uint32_t key = transpose ? ru * nb + cu / br : cu * nb + ru / br;
+        keys[e] = key;
+        vals[e] = weighted ? static_cast<uint32_t>(e) : static_cast<uint32_t>(transpose ? c : r);
+        if (transpose) atomicAdd(&degc[c], 1); // the normalisation always uses the in-degree over `col` (:66)
+    }
+}
+
+// kptr[j] = first position of the sorted keys holding a key >= j, for j in [0, n_keys]  (kptr[n_keys] = E): thread k
+// owns the gap between key[k-1] and key[k].  Replaces E atomic increments + a scan over the n_keys counters.
+__global__ __launch_bounds__(256) void csr_bounds_kernel(const uint32_t* __restrict__ key_sorted, int64_t E,
+                                                         int64_t n_keys, int32_t* __restrict__ kptr) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    for (int64_t k = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; k <= E; k += stride) {
+        const int64_t lo = (k == 0) ? 0 : static_cast<int64_t>(key_sorted[k - 1]) + 1;
+        const int64_t hi = (k == E) ? n_keys : static_cast<int64_t>(key_sorted[k]);
+        for (int64_t j = lo; j <= hi; ++j) kptr[j] = static_cast<int32_t>(k);
+    }
+}
+
+// From the key pointers kptr[dst*NB + blk]: rowptr, block-major blkptr, and
+// dinv[n] = sqrt(1/deg[n])  (float32, correctly rounded: difformer.py:67-68); deg 0 -> inf
+__global__ __launch_bounds__(256) void csr_ptrs_kernel(const int32_t* __restrict__ kptr, int64_t N, int64_t NB,
+                                                       int32_t* __restrict__ rowptr, int32_t* __restrict__ blkptr,
+                                                       const int32_t* __restrict__ degc, float* __restrict__ dinv,
+                                                       int32_t* __restrict__ longest) {
+    const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    int32_t len = 0;
+    if (r <= N) {
+        const int32_t start = kptr[r * NB];
+        rowptr[r] = start;                         // r == N: kptr[N*NB] = E
+        if (r < N) {
+            const int32_t end = kptr[(r + 1) * NB];
+            len = end - start;
+            dinv[r] = sqrtf(1.0f / static_cast<float>(degc ? degc[r] : end - start));
+            if (blkptr) {
+                for (int64_t b = 0; b < NB; ++b) blkptr[b * N + r] = kptr[r * NB + b];
+                blkptr[NB * N + r] = end;
+            }
+        }
+    }
+    // the longest row of the CSR (status[1]): one atomic per wave
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const int32_t o = __shfl_xor(len, off, 64); len = o > len ? o : len; }
+    if ((threadIdx.x & 63) == 0 && len > 0) atomicMax(longest, len);
 }
 
 // ---- rows of a shard by descending degree (load balance of the blocked SpMM) ----------------------
@@ -614,94 +705,12 @@ unsigned capped_blocks(int64_t blocks) {
 }
 unsigned capped_grid(int64_t n) { return capped_blocks((n + 255) / 256); }   // 256 threads per block
 
-int zero_async(const char* who, void* p, size_t bytes, hipStream_t st) {
-    const hipError_t he = hipMemsetAsync(p, 0, bytes, st);
-    return he == hipSuccess ? 0 : dif::fail(static_cast<int>(he), "%s: memset: %s", who, hipGetErrorString(he));
-}
-
-int check_workspace(const char* who, const void* workspace, size_t have, size_t need) {
-    DIF_REQUIRE(have >= need, DIF_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, have, need);
-    DIF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, DIF_E_BADARG, "%s: workspace must be 256-byte aligned", who);
-    return 0;
-}
-
 // n_batches of the three dif_subgraph_batches_* calls.  The group sort files dropped edges under key 0xffff, which has to
 // sort behind every batch.
 int batch_count(int64_t M, int64_t batch_size, int* n_batches) {
     const int64_t nb64 = (M + batch_size - 1) / batch_size;
     DIF_REQUIRE(nb64 < 65535, DIF_E_RANGE, "dif_subgraph_batches: at most 65,534 batches");
     *n_batches = static_cast<int>(nb64);
-    return 0;
-}
-
-// ---- workspace layout: 256-byte aligned pieces, one after the other --------------------------------------------------
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-struct Arena {
-    size_t o = 0;                                   // bytes taken so far = the total when the layout is complete
-    size_t take(size_t bytes) { const size_t at = o; o += align256(bytes); return at; }
-};
-
-// block sums of exclusive_scan over scan_n values (+ 1: the grand total)
-inline size_t scan_scratch_bytes(int64_t scan_n) { return static_cast<size_t>((scan_n + kScanTile - 1) / kScanTile + 1) * 4; }
-
-template <class T> T* at(char* ws, size_t off) { return reinterpret_cast<T*>(ws + off); }
-template <class T> const T* at(const char* ws, size_t off) { return reinterpret_cast<const T*>(ws + off); }
-
-// ---- the sort: geometry, buffers, the pass loop ----------------------------------------------------------------------
-struct SortGeom {
-    int64_t n;             // (key, payload) pairs
-    int rounds;            // 64-key rounds per wave chunk
-    int64_t n_chunks;      // sort chunks (waves)
-    int64_t table_len;     // kRadix * n_chunks
-    int passes;            // radix passes, kRadixBits of the key each
-};
-
-// passes that order keys in [0, n_keys)
-int key_passes(int64_t n_keys) {
-    int bits = 1;
-    while ((int64_t(1) << bits) < n_keys) ++bits;
-    return (bits + kRadixBits - 1) / kRadixBits;
-}
-
-// rounds = 0: from the item count
-SortGeom sort_geom(int64_t n, int passes, int64_t rounds = 0) {
-    SortGeom g;
-    g.n = n;
-    constexpr int64_t per_round = 64 * 4096;                         // aim at ~4096 waves
-    if (rounds == 0) rounds = (n + per_round - 1) / per_round;
-    if (rounds < kSortRoundsMin) rounds = kSortRoundsMin;
-    if (rounds > kSortRoundsMax) rounds = kSortRoundsMax;
-    g.rounds = static_cast<int>(rounds);
-    const int64_t chunk = 64 * rounds;
-    g.n_chunks = (n + chunk - 1) / chunk;
-    if (g.n_chunks < 1) g.n_chunks = 1;
-    g.table_len = g.n_chunks * kRadix;
-    g.passes = passes;
-    return g;
-}
-
-struct SortBufs {
-    uint32_t *kin, *kout;    // keys: what the next pass reads, what it writes
-    uint32_t *vin, *vout;    // payload, likewise
-    int32_t *table, *bsum;   // per-chunk digit counts [table_len] and the scratch of their scan
-};
-
-// g.passes stable passes over the pairs in (b.kin, b.vin), lowest digit first.  Every pass swaps the roles of the two pairs
-// of buffers, so on return b.kin / b.vin hold the sorted keys / payload wherever the last pass left them: in the pair that
-// came in as (kout, vout) after an odd number of passes, in the one that came in as (kin, vin) after an even number.
-int radix_sort(const SortGeom& g, SortBufs& b, hipStream_t st) {
-    const unsigned sort_grid = static_cast<unsigned>((g.n_chunks + kSortWaves - 1) / kSortWaves);
-    for (int pass = 0; pass < g.passes; ++pass) {
-        const int shift = pass * kRadixBits;
-        if (int rc = dif::launch("radix_hist_kernel", radix_hist_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin, g.n,
-                                 shift, g.n_chunks, g.rounds, b.table)) return rc;
-        if (int rc = exclusive_scan(b.table, g.table_len, b.table, nullptr, b.bsum, st)) return rc;
-        if (int rc = dif::launch("radix_scatter_kernel", radix_scatter_kernel, dim3(sort_grid), dim3(64 * kSortWaves), 0, st, b.kin,
-                                 b.vin, g.n, shift, g.n_chunks, g.rounds, b.table, b.kout, b.vout)) return rc;
-        uint32_t* t = b.kin; b.kin = b.kout; b.kout = t;
-        t = b.vin; b.vin = b.vout; b.vout = t;
-    }
     return 0;
 }
 
@@ -1097,3 +1106,5 @@ extern "C" int dif_graph_prepare(const int64_t* edge_index, int64_t E, int64_t N
     return dif::launch("prep_emit_kernel", prep_emit_kernel, dim3(capped_grid(n > N ? n : N)), dim3(256), 0, st, row, col, n, keep,
                        N, add_loops, capacity, out_edge_index, out_count);
 }
+
+#endif  // DIF_GCN_CSR_SORT_ONLY

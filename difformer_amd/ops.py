@@ -174,13 +174,13 @@ SLICED_MAX_PARTS = 64       # one slot
 # quad may be read by two lanes of a step -- fewer padded steps for a few 2-way shared LDS reads, a longer cold build.
 # DIFFORMER_SLICED_SCHEDULE = strict | packed | auto (default); auto packs where the build is paid back within 64
 # launches (one short training run, or a few evaluations of a 4-layer model).  Measured on the MI355X at F = 64
-# (profiles/r07_experiments.md): a launch saves
-#    2.4 M entries: 1.4 us    10 M: 8 us    30 M: 15 us    79 M (headline): 42 us        (scripts/exp_slot_order.py)
-# and the cold build of CSR + format, as `bench.py --full` times it on the headline graph, goes from 8.0 to 9.9 ms
-# (the slot order's sort, the indirection through `order`, their host side; back to back in one warm process the
-# format build alone differs by 0.55-0.75 ms at every size).  1.9 ms / 64 = 30 us per launch: between the 30 M and
-# the 79 M point, ~57 M entries by interpolation.
-SLICED_PACKED_MIN_ENTRIES = 60_000_000
+# (profiles/r07_experiments.md, profiles/r12_experiments.md): against the strict schedule a launch saves
+#    2.4 M entries: 1.4 us    10 M: 8 us    30 M: 15 us    79 M (headline): 35 us, 41 us with the dealt slot order
+# and the cold build of CSR + format, as `bench.py --full` times it on the headline graph, goes from 9.1 ms (strict) to
+# 10.0 ms (packed_slot_order) and 11.6 ms (the dealt order: 1.9 ms of device time for its two sorts, the greedy windows and
+# the deal).  2.45 ms / 64 = 38 us per launch: linear between the 30 M point (17 us with the dealt order's share) and the
+# 79 M point (41 us) that is ~73 M entries.
+SLICED_PACKED_MIN_ENTRIES = 72_000_000
 SLICED_PACKED_MAX_TILES = 40  # the slot order's key holds one bit per tile in an int64
 
 
@@ -189,6 +189,25 @@ def sliced_schedule():
     if mode not in ("strict", "packed", "auto"):
         raise ValueError(f"DIFFORMER_SLICED_SCHEDULE={mode!r}: expected strict, packed or auto")
     return mode
+
+
+# Which rows share a slot of the packed schedule, and which slots share a wave:
+# DIFFORMER_SLICED_SLOTS = dealt (default): greedy slots by tile profile, dealt to the waves against their running envelope,
+# all on the device (csrc/sliced_slots.hip); profile: packed_slot_order below, slots dealt in order -- also what a geometry
+# the device call does not cover gets.
+def sliced_slots():
+    mode = os.environ.get("DIFFORMER_SLICED_SLOTS", "dealt").strip().lower() or "dealt"
+    if mode not in ("profile", "dealt"):
+        raise ValueError(f"DIFFORMER_SLICED_SLOTS={mode!r}: expected profile or dealt")
+    return mode
+
+
+def packed_order(be, rowptr, blkptr, n_src, NT, row_begin, n_rows, plan):
+    """The row order of the packed schedule under DIFFORMER_SLICED_SLOTS: int32 [n_rows] on the device."""
+    order = None
+    if sliced_slots() == "dealt" and hasattr(be, "sliced_slot_order"):
+        order = be.sliced_slot_order(rowptr, blkptr, n_src, row_begin, n_rows, plan)
+    return packed_slot_order(rowptr, blkptr, n_src, NT, row_begin, n_rows) if order is None else order
 
 
 def packed_slot_order(rowptr, blkptr, n_src, NT, row_begin, n_rows):
@@ -339,7 +358,7 @@ class GraphCSR:
                 if plan is None or int(plan[6]) != T or int(plan[7]) != NT:
                     return None
         elif NT <= SLICED_PACKED_MAX_TILES and (mode == "packed" or (mode == "auto" and total >= SLICED_PACKED_MIN_ENTRIES)):
-            order = packed_slot_order(self.rowptr, self.blkptr, self.num_nodes, NT, row_begin, n_rows)
+            order = packed_order(be, self.rowptr, self.blkptr, self.num_nodes, NT, row_begin, n_rows, plan)
             quad_cap = 2
         built = be.sliced_build(self.rowptr, self.blkptr, self.src, self.num_nodes, self.nnz, row_begin, n_rows, F, plan, order,
                                 parts, n_pos, quad_cap)
