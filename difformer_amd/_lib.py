@@ -25,6 +25,9 @@ KNN_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difform
 # the slot-order library of the packed sliced schedule (C ABI: include/difformer_slots.h), loaded on first use by load_slots()
 SLOTS_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_slots.so")
 SLOTS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_slots.h"))
+# the evaluation-metric library (C ABI: include/difformer_metrics.h), loaded on first use by load_metrics()
+METRICS_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_metrics.so")
+METRICS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_metrics.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -141,11 +144,17 @@ _slots_code = _read_header(SLOTS_HEADER_PATH)
 SLOTS_VERSION = _defines(_slots_code, "DIF_SLOTS_VERSION")["DIF_SLOTS_VERSION"]
 SLOTS_SIGNATURES = _prototypes(_slots_code)
 
+# ... and include/difformer_metrics.h of the sixth's
+_metrics_code = _read_header(METRICS_HEADER_PATH)
+METRICS_VERSION = _defines(_metrics_code, "DIF_METRICS_VERSION")["DIF_METRICS_VERSION"]
+METRICS_SIGNATURES = _prototypes(_metrics_code)
+
 _lib = None
 _maps = None
 _edges = None
 _knn = None
 _slots = None
+_metrics = None
 
 
 class DifformerHipError(RuntimeError):
@@ -248,6 +257,14 @@ def load_slots():
     return _slots
 
 
+def load_metrics():
+    """Load libdifformer_metrics.so once."""
+    global _metrics
+    if _metrics is None:
+        _metrics = _load_side(METRICS_LIB_PATH, METRICS_SIGNATURES, "dif_metrics_version", METRICS_VERSION)
+    return _metrics
+
+
 def check_maps(rc, what):
     """check() for a call into libdifformer_maps.so: the message comes from that library."""
     if rc != 0:
@@ -273,6 +290,13 @@ def check_slots(rc, what):
     """check() for a call into libdifformer_slots.so: the message comes from that library."""
     if rc != 0:
         msg = load_slots().dif_slots_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
+
+
+def check_metrics(rc, what):
+    """check() for a call into libdifformer_metrics.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_metrics().dif_metrics_last_error()
         raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 

@@ -219,17 +219,17 @@ class HipBackend:
         torch.cuda.synchronize()
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
-    def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False, slots=False):
+    def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False, slots=False, metrics=False):
         """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
         a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
         `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
-        collection, operands on the current device -- adds nothing around the call.  maps / edges / knn / slots: `symbol` is
-        one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so (include/difformer_edges.h) /
-        libdifformer_knn.so (include/difformer_knn.h) / libdifformer_slots.so (include/difformer_slots.h), loaded on first
-        use."""
-        side = (_lib.load_maps, _lib.check_maps) if maps else ((_lib.load_edges, _lib.check_edges) if edges else
-                                                               ((_lib.load_knn, _lib.check_knn) if knn else
-                                                                ((_lib.load_slots, _lib.check_slots) if slots else None)))
+        collection, operands on the current device -- adds nothing around the call.  maps / edges / knn / slots / metrics:
+        `symbol` is one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so
+        (include/difformer_edges.h) / libdifformer_knn.so (include/difformer_knn.h) / libdifformer_slots.so
+        (include/difformer_slots.h) / libdifformer_metrics.so (include/difformer_metrics.h), loaded on first use."""
+        side = ((_lib.load_maps, _lib.check_maps) if maps else (_lib.load_edges, _lib.check_edges) if edges else
+                (_lib.load_knn, _lib.check_knn) if knn else (_lib.load_slots, _lib.check_slots) if slots else
+                (_lib.load_metrics, _lib.check_metrics) if metrics else None)
         fn = getattr(side[0]() if side else self.lib, symbol)
         index = dev.index
         if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
@@ -413,6 +413,54 @@ class HipBackend:
         self._call("dif_knn_graph_f32", "dif_knn_graph_f32", dev, _ptr(x), ldx, N, M, int(k), int(bool(loop)), int(metric),
                    int(centre_row), int(route), _ptr(edge_index), _ptr(dist), _ptr(ws), ws_bytes, knn=True)
         return edge_index, dist
+
+    # ---- evaluation metrics (libdifformer_metrics.so) ---------------------------------------------
+    def rocauc_counts(self, score, cls):
+        """score [n,C] float32 and cls [n,C] uint8 class codes (0 negative, 1 positive, 2 unlabelled, 3 another value), rows of
+        unit column stride -> int64 [C,5] = per column {P, N, unlabelled, invalid, U2}: roc_auc_score of a column is
+        U2 / (2 P N) (csrc/eval_metrics.hip).  n C <= 2^31 - 1: the caller (metrics.py) cuts the columns into groups."""
+        dev = _require_device(score, cls)
+        _all_f32(score=score)
+        n, C = score.shape
+        if cls.dtype != torch.uint8 or tuple(cls.shape) != (n, C):
+            raise ValueError(f"difformer_amd: rocauc_counts takes uint8 class codes of shape {(n, C)} (got {cls.dtype}, "
+                             f"{tuple(cls.shape)})")
+        if score.stride(1) != 1 and C > 1:
+            score = score.contiguous()
+        if cls.stride(1) != 1 and C > 1:
+            cls = cls.contiguous()
+        lds = int(score.stride(0)) if n > 1 else C
+        ldc = int(cls.stride(0)) if n > 1 else C
+        if lds < C:
+            score, lds = score.contiguous(), C
+        if ldc < C:
+            cls, ldc = cls.contiguous(), C
+        met = _lib.load_metrics()
+        counts = torch.empty((C, 5), dtype=torch.int64, device=dev)
+        ws_bytes = met.dif_rocauc_workspace_bytes(n, C)
+        ws = _workspace(ws_bytes, dev, floor=16)
+        self._call("dif_rocauc_counts_f32", "dif_rocauc_counts_f32", dev, _ptr(score), lds, _ptr(cls), ldc, n, C, _ptr(counts),
+                   _ptr(ws), ws_bytes, metrics=True)
+        return counts
+
+    def argmax_correct(self, pred, label, labelled):
+        """pred [n,K] float32 (rows of unit column stride), label int64 [n], labelled uint8 [n] -> int64 [2] = {labelled rows
+        whose first maximal index (NaN above every number) equals the label, labelled rows} (csrc/eval_metrics.hip)."""
+        dev = _require_device(pred, label, labelled)
+        _all_f32(pred=pred)
+        n, K = pred.shape
+        if label.dtype != torch.int64 or labelled.dtype != torch.uint8 or label.shape != (n,) or labelled.shape != (n,):
+            raise ValueError(f"difformer_amd: argmax_correct takes int64 labels and a uint8 mask of shape ({n},)")
+        if pred.stride(1) != 1 and K > 1:
+            pred = pred.contiguous()
+        ldp = int(pred.stride(0)) if n > 1 else K
+        if ldp < K:
+            pred, ldp = pred.contiguous(), K
+        label, labelled = label.contiguous(), labelled.contiguous()
+        out = torch.empty(2, dtype=torch.int64, device=dev)
+        self._call("dif_argmax_correct_f32", "dif_argmax_correct_f32", dev, _ptr(pred), ldp, _ptr(label), _ptr(labelled), n, K,
+                   _ptr(out), metrics=True)
+        return out
 
     # ---- attention on graph edges (libdifformer_edges.so) ----------------------------------------
     def edge_attention(self, q, k, scale, edge_index, mode):
