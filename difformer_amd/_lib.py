@@ -28,6 +28,9 @@ SLOTS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "diffo
 # the evaluation-metric library (C ABI: include/difformer_metrics.h), loaded on first use by load_metrics()
 METRICS_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_metrics.so")
 METRICS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_metrics.h"))
+# the training-loss library (C ABI: include/difformer_loss.h), loaded on first use by load_loss()
+LOSS_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_loss.so")
+LOSS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_loss.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -149,12 +152,19 @@ _metrics_code = _read_header(METRICS_HEADER_PATH)
 METRICS_VERSION = _defines(_metrics_code, "DIF_METRICS_VERSION")["DIF_METRICS_VERSION"]
 METRICS_SIGNATURES = _prototypes(_metrics_code)
 
+# ... and include/difformer_loss.h of the seventh's
+_loss_code = _read_header(LOSS_HEADER_PATH)
+LOSS_VERSION = _defines(_loss_code, "DIF_LOSS_VERSION")["DIF_LOSS_VERSION"]
+LOSS_CONSTANTS = _defines(_loss_code, r"DIF_LOSS_(?:ROWS|TARGET|RECORD)_\w+")      # rows_kind / target_type codes, record size
+LOSS_SIGNATURES = _prototypes(_loss_code)
+
 _lib = None
 _maps = None
 _edges = None
 _knn = None
 _slots = None
 _metrics = None
+_loss = None
 
 
 class DifformerHipError(RuntimeError):
@@ -265,6 +275,14 @@ def load_metrics():
     return _metrics
 
 
+def load_loss():
+    """Load libdifformer_loss.so once."""
+    global _loss
+    if _loss is None:
+        _loss = _load_side(LOSS_LIB_PATH, LOSS_SIGNATURES, "dif_loss_version", LOSS_VERSION)
+    return _loss
+
+
 def check_maps(rc, what):
     """check() for a call into libdifformer_maps.so: the message comes from that library."""
     if rc != 0:
@@ -297,6 +315,13 @@ def check_metrics(rc, what):
     """check() for a call into libdifformer_metrics.so: the message comes from that library."""
     if rc != 0:
         msg = load_metrics().dif_metrics_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
+
+
+def check_loss(rc, what):
+    """check() for a call into libdifformer_loss.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_loss().dif_loss_last_error()
         raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 

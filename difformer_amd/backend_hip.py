@@ -130,6 +130,15 @@ def _workspace(nbytes, dev, floor=0, or_none=False):
     return torch.empty(max(nbytes, floor), dtype=torch.uint8, device=dev)
 
 
+def _loss_rows(t, C):
+    """[n, C] operand of a loss kernel -> (tensor, leading dimension in elements).  Rows of unit column stride at least C
+    apart are taken as they are, aligned to their element only; anything else (a column step, overlapping rows) is copied."""
+    n = t.shape[0]
+    if (t.stride(1) != 1 and C > 1) or (n > 1 and t.stride(0) < C):
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if n > 1 else C)
+
+
 def _slice_major(F, plan, dev):
     """ys [F/4, T*NT, 4]: the slice-major copy of [n, F] rows that sliced_spmm reads (plan: sliced_plan's geometry)."""
     return torch.empty((F // 4, int(plan[6]) * int(plan[7]), 4), dtype=torch.float32, device=dev)
@@ -219,17 +228,18 @@ class HipBackend:
         torch.cuda.synchronize()
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
-    def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False, slots=False, metrics=False):
+    def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False, slots=False, metrics=False, loss=False):
         """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
         a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
         `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
-        collection, operands on the current device -- adds nothing around the call.  maps / edges / knn / slots / metrics:
-        `symbol` is one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so
+        collection, operands on the current device -- adds nothing around the call.  maps / edges / knn / slots / metrics /
+        loss: `symbol` is one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so
         (include/difformer_edges.h) / libdifformer_knn.so (include/difformer_knn.h) / libdifformer_slots.so
-        (include/difformer_slots.h) / libdifformer_metrics.so (include/difformer_metrics.h), loaded on first use."""
+        (include/difformer_slots.h) / libdifformer_metrics.so (include/difformer_metrics.h) / libdifformer_loss.so
+        (include/difformer_loss.h), loaded on first use."""
         side = ((_lib.load_maps, _lib.check_maps) if maps else (_lib.load_edges, _lib.check_edges) if edges else
                 (_lib.load_knn, _lib.check_knn) if knn else (_lib.load_slots, _lib.check_slots) if slots else
-                (_lib.load_metrics, _lib.check_metrics) if metrics else None)
+                (_lib.load_metrics, _lib.check_metrics) if metrics else (_lib.load_loss, _lib.check_loss) if loss else None)
         fn = getattr(side[0]() if side else self.lib, symbol)
         index = dev.index
         if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
@@ -461,6 +471,77 @@ class HipBackend:
         self._call("dif_argmax_correct_f32", "dif_argmax_correct_f32", dev, _ptr(pred), ldp, _ptr(label), _ptr(labelled), n, K,
                    _ptr(out), metrics=True)
         return out
+
+    # ---- training losses (libdifformer_loss.so) ---------------------------------------------------
+    def loss_row_weights(self, index, n):
+        """int64 index [m] (any order, duplicates count) -> (int32 [n] multiplicity of every row, int32 [1] number of indices
+        outside [0, n)); integer atomics only (csrc/loss.hip)."""
+        dev = _require_device(index)
+        if index.dtype != torch.int64 or index.dim() != 1:
+            raise ValueError(f"difformer_amd: loss_row_weights takes a 1-d int64 index (got {index.dtype}, {tuple(index.shape)})")
+        index = index.contiguous()
+        weight = torch.empty(n, dtype=torch.int32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        self._call("dif_loss_row_weights", "dif_loss_row_weights", dev, _ptr(index), index.shape[0], n, _ptr(weight), _ptr(status),
+                   loss=True)
+        return weight, status
+
+    @staticmethod
+    def _loss_operands(kind, out, second, rows, ignore_index):
+        """The leading arguments the forward and the backward of one loss share: logits [n,C] and, for kind 'nll', int64 labels
+        [n], for 'bce' a target [n,C] of int64 / float32 / uint8, both as row-strided views (stride(0) is the leading
+        dimension: a column slice is NOT copied); rows None | int32 [n] weights | uint8 [n] mask.
+        -> (device, suffix, n, C, arguments up to rows_kind, tensors to keep alive)."""
+        dev = _require_device(out, second, rows)
+        _, sfx = _storage(out)
+        n, C = out.shape
+        out, ldx = _loss_rows(out, C)
+        const = _lib.LOSS_CONSTANTS
+        if rows is None:
+            rows_kind = const["DIF_LOSS_ROWS_ALL"]
+        elif rows.dtype == torch.int32 and rows.shape == (n,):
+            rows, rows_kind = rows.contiguous(), const["DIF_LOSS_ROWS_WEIGHTS"]
+        elif rows.dtype == torch.uint8 and rows.shape == (n,):
+            rows, rows_kind = rows.contiguous(), const["DIF_LOSS_ROWS_MASK"]
+        else:
+            raise ValueError(f"difformer_amd: the row selection of a loss is int32 weights or a uint8 mask of shape ({n},) "
+                             f"(got {rows.dtype}, {tuple(rows.shape)})")
+        if kind == "nll":
+            if second.dtype != torch.int64 or second.shape != (n,):
+                raise ValueError(f"difformer_amd: the NLL takes int64 labels of shape ({n},) (got {second.dtype}, {tuple(second.shape)})")
+            second = second.contiguous()
+            args = (_ptr(out), ldx, _ptr(second), int(ignore_index), _ptr(rows), rows_kind)
+        else:
+            types = {torch.int64: "DIF_LOSS_TARGET_I64", torch.float32: "DIF_LOSS_TARGET_F32", torch.uint8: "DIF_LOSS_TARGET_U8"}
+            if second.dtype not in types or tuple(second.shape) != (n, C):
+                raise ValueError(f"difformer_amd: the BCE takes an int64, float32 or uint8 target of shape {(n, C)} "
+                                 f"(got {second.dtype}, {tuple(second.shape)})")
+            second, ldt = _loss_rows(second, C)
+            args = (_ptr(out), ldx, _ptr(second), const[types[second.dtype]], ldt, _ptr(rows), rows_kind)
+        return dev, sfx, n, C, args, (out, second, rows)
+
+    def loss_forward(self, kind, out, second, rows=None, index_status=None, ignore_index=-100):
+        """-> the 32-byte record of include/difformer_loss.h as float64 [4]: [0] the loss, .view(float32)[2] the loss rounded
+        to float32, .view(int64)[2] count, .view(int64)[3] invalid.  index_status: loss_row_weights' status word."""
+        dev, sfx, n, C, args, keep = self._loss_operands(kind, out, second, rows, ignore_index)
+        lib = _lib.load_loss()
+        record = torch.empty(4, dtype=torch.float64, device=dev)
+        ws_bytes = lib.dif_loss_workspace_bytes(n, C)
+        ws = _workspace(ws_bytes, dev, floor=16)
+        symbol = ("dif_nll_log_softmax_fwd_" if kind == "nll" else "dif_bce_with_logits_fwd_") + sfx
+        self._call(symbol, symbol, dev, *args, _ptr(index_status), n, C, _ptr(record), _ptr(ws), ws_bytes, loss=True)
+        return record
+
+    def loss_backward(self, kind, out, second, record, upstream, rows=None, ignore_index=-100):
+        """-> d loss / d out [n,C] in out's dtype, every element written (csrc/loss.hip).  upstream: float32 scalar on the device."""
+        dev, sfx, n, C, args, keep = self._loss_operands(kind, out, second, rows, ignore_index)
+        _require_device(record, upstream)
+        if upstream.dtype != torch.float32 or upstream.numel() != 1:
+            raise ValueError(f"difformer_amd: the upstream gradient of a loss is one float32 (got {upstream.dtype}, {tuple(upstream.shape)})")
+        grad = torch.empty((n, C), dtype=out.dtype, device=dev)
+        symbol = ("dif_nll_log_softmax_bwd_" if kind == "nll" else "dif_bce_with_logits_bwd_") + sfx
+        self._call(symbol, symbol, dev, *args, n, C, _ptr(record), _ptr(upstream), _ptr(grad), C, loss=True)
+        return grad
 
     # ---- attention on graph edges (libdifformer_edges.so) ----------------------------------------
     def edge_attention(self, q, k, scale, edge_index, mode):

@@ -98,13 +98,15 @@ def graphed_training(model, x, edge_index=None, edge_weight=None, warmup=3):
 class GraphedTrainStep:
     """One optimisation step -- forward, loss, backward, optimiser update (main.py:117-131) -- captured as ONE hipGraph.
 
-        step = difformer_amd.GraphedTrainStep(model, optimizer, lambda out: F.nll_loss(F.log_softmax(out, 1)[idx], y[idx]),
+        step = difformer_amd.GraphedTrainStep(model, optimizer, lambda out: difformer_amd.log_softmax_nll(out, y, train_mask),
                                               x, edge_index)
         for epoch in range(epochs):
             loss = step()                  # replays; `loss` is the captured scalar tensor (read it with float(loss))
 
     The optimiser must be capturable (torch.optim.Adam(..., capturable=True), SGD, ...) and `loss_fn` must only enqueue
-    device work (no .item() / host syncs); operands keep their shapes and the graph its edges.  A Cora-sized step: 1.8-2.0 ms
+    device work (no .item() / host syncs): `out[train_mask]` with a boolean mask calls `nonzero`, which waits for the host and
+    cannot be captured -- `log_softmax_nll` / `bce_with_logits` (losses.py) take the mask as it is, and an index expression such as
+    `F.nll_loss(F.log_softmax(out, 1)[idx], y[idx])` is fine too.  Operands keep their shapes and the graph its edges.  A Cora-sized step: 1.8-2.0 ms
     kernel by kernel, 0.9 ms with graphed_training, 0.67 ms this way."""
 
     def __init__(self, model, optimizer, loss_fn, x, edge_index=None, edge_weight=None, warmup=3):

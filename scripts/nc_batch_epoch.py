@@ -3,7 +3,9 @@
     batch's training nodes -> backward -> Adam
   ogbn-proteins  132,534 nodes, 79.3 M directed entries, 8 features, 112 labels (BCE), hidden 64, 3 layers, batches of 10,000
   pokec          1,632,803 nodes, 30.6 M directed entries + loops, 65 features, 2 classes (NLL), hidden 128, 3 layers, batches of 100,000
-Synthetic graphs of those sizes.    python scripts/nc_batch_epoch.py [proteins|pokec]"""
+Synthetic graphs of those sizes.    python scripts/nc_batch_epoch.py [proteins|pokec] [--device-loss]
+--device-loss: the loss on the batch's training nodes through difformer_amd.losses (csrc/loss.hip: the boolean mask becomes a row
+weight, no `out[m]`); without it the tensor-operation expression of main-batch.py:136-140, the comparison."""
 import os
 import sys
 import time
@@ -13,10 +15,11 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from difformer_amd import DIFFormer, graph_utils as gu  # noqa: E402
+from difformer_amd import DIFFormer, bce_with_logits, graph_utils as gu, log_softmax_nll  # noqa: E402
 
 dev = torch.device("cuda:0")
-which = sys.argv[1:] or ["proteins", "pokec"]
+DEVICE_LOSS = "--device-loss" in sys.argv[1:]
+which = [a for a in sys.argv[1:] if a != "--device-loss"] or ["proteins", "pokec"]
 CFG = {"proteins": (132534, 39561252, 8, 112, 64, 10000, "bce"), "pokec": (1632803, 15311282, 65, 2, 128, 100000, "nll")}
 for name in which:
     N, PAIRS, F_IN, C, HIDDEN, BATCH, LOSS = CFG[name]
@@ -48,7 +51,9 @@ for name in which:
             opt.zero_grad()
             out = model(x[idx], ei)
             m = train_mask[idx]
-            if LOSS == "bce":
+            if DEVICE_LOSS:
+                loss = bce_with_logits(out, y[idx], m) if LOSS == "bce" else log_softmax_nll(out, y[idx], m)
+            elif LOSS == "bce":
                 loss = F.binary_cross_entropy_with_logits(out[m], y[idx][m])
             else:
                 loss = F.nll_loss(F.log_softmax(out, dim=1)[m], y[idx][m])
@@ -61,7 +66,7 @@ for name in which:
     epoch()
     t, nb, e_last = epoch()
     tot = t["subgraph"] + t["step"]
-    print(f"{name}: {nb} batches of {BATCH} (last subgraph {e_last} entries): epoch {tot * 1e3:.1f} ms = subgraph {t['subgraph'] / nb * 1e3:.2f} ms + "
+    print(f"{name} ({'device loss' if DEVICE_LOSS else 'torch loss'}): {nb} batches of {BATCH} (last subgraph {e_last} entries): epoch {tot * 1e3:.1f} ms = subgraph {t['subgraph'] / nb * 1e3:.2f} ms + "
           f"training step {t['step'] / nb * 1e3:.2f} ms per batch", flush=True)
     model.eval()
     with torch.no_grad():
