@@ -9,7 +9,8 @@ include/difformer_hip.h) and, for the attention maps, lib/libdifformer_maps.so (
 include/difformer_maps.h) and lib/libdifformer_edges.so (at the edges of a graph, include/difformer_edges.h); k-nearest-neighbour
 graphs come from lib/libdifformer_knn.so (include/difformer_knn.h), the evaluation metrics from lib/libdifformer_metrics.so
 (include/difformer_metrics.h), the training losses (masked log-softmax NLL, BCE with logits) from lib/libdifformer_loss.so
-(include/difformer_loss.h).  Importing this package does not load the library; the first operator
+(include/difformer_loss.h), the Adam update of a whole model in one launch from lib/libdifformer_adam.so
+(include/difformer_adam.h).  Importing this package does not load the library; the first operator
 call does, and fails loudly if it has not been built.
 """
 from .attention_maps import attention_on_edges, attention_topk  # noqa: F401
@@ -20,9 +21,10 @@ from .graphs import GraphedForward, GraphedTrainStep, graphed_training  # noqa: 
 from .losses import bce_with_logits, log_softmax_nll, loss_record  # noqa: F401
 from .metrics import eval_acc, eval_f1, eval_rocauc, rocauc_counts  # noqa: F401
 from .neighbors import kneighbors_graph, knn_graph  # noqa: F401
+from .optim import Adam  # noqa: F401
 
 __all__ = ["DIFFormer", "DIFFormerConv", "full_attention_conv", "gcn_conv", "DIFFormer_v2", "TransConv", "RowShard",
            "GraphedForward", "GraphedTrainStep", "graphed_training", "attention_topk", "attention_on_edges", "knn_graph",
            "kneighbors_graph", "eval_rocauc", "eval_acc", "eval_f1", "rocauc_counts", "log_softmax_nll",
-           "bce_with_logits", "loss_record"]
+           "bce_with_logits", "loss_record", "Adam"]
 __version__ = "0.1.0"

@@ -31,6 +31,9 @@ METRICS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "dif
 # the training-loss library (C ABI: include/difformer_loss.h), loaded on first use by load_loss()
 LOSS_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_loss.so")
 LOSS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_loss.h"))
+# the optimiser library (C ABI: include/difformer_adam.h), loaded on first use by load_adam()
+ADAM_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_adam.so")
+ADAM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_adam.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -158,6 +161,12 @@ LOSS_VERSION = _defines(_loss_code, "DIF_LOSS_VERSION")["DIF_LOSS_VERSION"]
 LOSS_CONSTANTS = _defines(_loss_code, r"DIF_LOSS_(?:ROWS|TARGET|RECORD)_\w+")      # rows_kind / target_type codes, record size
 LOSS_SIGNATURES = _prototypes(_loss_code)
 
+# ... and include/difformer_adam.h of the eighth's
+_adam_code = _read_header(ADAM_HEADER_PATH)
+ADAM_VERSION = _defines(_adam_code, "DIF_ADAM_VERSION")["DIF_ADAM_VERSION"]
+ADAM_CONSTANTS = _defines(_adam_code, r"DIF_ADAM_(?:MAX_TENSORS|CHUNK|TABLE_FIELDS|TICKET_BYTES)")   # launch geometry, table row, tickets
+ADAM_SIGNATURES = _prototypes(_adam_code)
+
 _lib = None
 _maps = None
 _edges = None
@@ -165,6 +174,7 @@ _knn = None
 _slots = None
 _metrics = None
 _loss = None
+_adam = None
 
 
 class DifformerHipError(RuntimeError):
@@ -283,6 +293,14 @@ def load_loss():
     return _loss
 
 
+def load_adam():
+    """Load libdifformer_adam.so once."""
+    global _adam
+    if _adam is None:
+        _adam = _load_side(ADAM_LIB_PATH, ADAM_SIGNATURES, "dif_adam_version", ADAM_VERSION)
+    return _adam
+
+
 def check_maps(rc, what):
     """check() for a call into libdifformer_maps.so: the message comes from that library."""
     if rc != 0:
@@ -322,6 +340,13 @@ def check_loss(rc, what):
     """check() for a call into libdifformer_loss.so: the message comes from that library."""
     if rc != 0:
         msg = load_loss().dif_loss_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
+
+
+def check_adam(rc, what):
+    """check() for a call into libdifformer_adam.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_adam().dif_adam_last_error()
         raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 

@@ -216,6 +216,7 @@ class HipBackend:
         self.kernel_events_only = None
         self._ones = {}                             # device -> float32 [1] = 1.0 (device-side beta of dif_rowgemm_f32)
         self._packed = TensorCache(64)              # weight tensor, geometry -> its packed copy (_cached_pack)
+        self._adam_tickets = {}                     # device -> int32 [DIF_ADAM_MAX_TENSORS], all zero between calls (adam_step)
         from . import ops
         self.lib.dif_set_exact_fp32(1 if ops.EXACT_FP32 else 0)      # a set_exact_fp32 made before the library was loaded
 
@@ -228,18 +229,20 @@ class HipBackend:
         torch.cuda.synchronize()
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
-    def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False, slots=False, metrics=False, loss=False):
+    def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False, slots=False, metrics=False, loss=False,
+              adam=False):
         """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
         a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
         `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
         collection, operands on the current device -- adds nothing around the call.  maps / edges / knn / slots / metrics /
-        loss: `symbol` is one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so
+        loss / adam: `symbol` is one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so
         (include/difformer_edges.h) / libdifformer_knn.so (include/difformer_knn.h) / libdifformer_slots.so
         (include/difformer_slots.h) / libdifformer_metrics.so (include/difformer_metrics.h) / libdifformer_loss.so
-        (include/difformer_loss.h), loaded on first use."""
+        (include/difformer_loss.h) / libdifformer_adam.so (include/difformer_adam.h), loaded on first use."""
         side = ((_lib.load_maps, _lib.check_maps) if maps else (_lib.load_edges, _lib.check_edges) if edges else
                 (_lib.load_knn, _lib.check_knn) if knn else (_lib.load_slots, _lib.check_slots) if slots else
-                (_lib.load_metrics, _lib.check_metrics) if metrics else (_lib.load_loss, _lib.check_loss) if loss else None)
+                (_lib.load_metrics, _lib.check_metrics) if metrics else (_lib.load_loss, _lib.check_loss) if loss else
+                (_lib.load_adam, _lib.check_adam) if adam else None)
         fn = getattr(side[0]() if side else self.lib, symbol)
         index = dev.index
         if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
@@ -471,6 +474,33 @@ class HipBackend:
         self._call("dif_argmax_correct_f32", "dif_argmax_correct_f32", dev, _ptr(pred), ldp, _ptr(label), _ptr(labelled), n, K,
                    _ptr(out), metrics=True)
         return out
+
+    # ---- the optimiser update (libdifformer_adam.so) ----------------------------------------------
+    def adam_step(self, params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, weight_decay):
+        """One Adam step (csrc/adam.hip; formula and rounding: include/difformer_adam.h) of params[i] under grads[i], in place,
+        with the moments exp_avgs[i] / exp_avg_sqs[i] and the float32 0-d step counters steps[i], which the kernel increments.
+        Dense float32 tensors on one device, aligned to their element; ceil(len / DIF_ADAM_MAX_TENSORS) launches on the current
+        stream, no host synchronisation.  The caller bumps the parameters' version counters."""
+        if not params:
+            return
+        dev = _require_device(*params)
+        table = []
+        for p, g, m, v, t in zip(params, grads, exp_avgs, exp_avg_sqs, steps, strict=True):
+            n = p.numel()
+            for name, x in (("param", p), ("grad", g), ("exp_avg", m), ("exp_avg_sq", v)):
+                if x.dtype != torch.float32 or x.device != dev or x.numel() != n or not x.is_contiguous():
+                    raise ValueError(f"difformer_amd: adam_step: {name} must be a dense float32 tensor of {n} elements on {dev} "
+                                     f"(got {x.dtype}, {tuple(x.shape)}, strides {x.stride()}, {x.device})")
+            if t.dtype != torch.float32 or t.device != dev or t.numel() != 1:
+                raise ValueError(f"difformer_amd: adam_step: step must be one float32 on {dev} (got {t.dtype}, {tuple(t.shape)}, {t.device})")
+            table += (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), t.data_ptr(), n)
+        tickets = self._adam_tickets.get(dev)
+        if tickets is None:
+            tickets = self._adam_tickets[dev] = torch.zeros(_lib.ADAM_CONSTANTS["DIF_ADAM_TICKET_BYTES"] // 4, dtype=torch.int32,
+                                                            device=dev)
+        rows = (ctypes.c_int64 * len(table))(*table)
+        self._call("dif_adam_step_f32", "dif_adam_step_f32", dev, rows, len(params), lr, beta1, beta2, eps, weight_decay,
+                   _ptr(tickets), adam=True)
 
     # ---- training losses (libdifformer_loss.so) ---------------------------------------------------
     def loss_row_weights(self, index, n):

@@ -1,7 +1,7 @@
 """Epoch of the image-and-text training loop (image and text/main.py:94-117) at the scripts' configurations (run.sh: 2 layers, hidden
 300 / 400, --use_residual --use_bn --alpha 0.5, no graph, no Wv... `use_weight` as parse.py leaves it; 10 classes): one training step
 (forward, log_softmax + nll on the labelled rows, backward, Adam with weight decay) + one evaluation forward, on synthetic features.
-    python scripts/it_epoch.py [--epochs 20]"""
+    python scripts/it_epoch.py [--epochs 20] [--optimizer torch|fused|capturable|difformer]"""
 import argparse
 import os
 import sys
@@ -19,6 +19,7 @@ ap.add_argument("--epochs", type=int, default=20)
 ap.add_argument("--only", default="")
 ap.add_argument("--kernel", default="")
 ap.add_argument("--train-only", action="store_true")
+ap.add_argument("--optimizer", default="torch", help="torch (torch.optim.Adam, the default) | fused | capturable | difformer (difformer_amd.Adam)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 print(f"{'dataset':10s} {'kernel':8s} {'N':>6s} {'hidden':>6s} {'train step ms':>14s} {'eval forward ms':>16s} {'epoch ms':>9s}")
@@ -31,7 +32,11 @@ for name, n, f_in, hidden, classes in (("stl10", 13000, 512, 400, 10), ("cifar10
         torch.manual_seed(0)
         model = DIFFormer(f_in, hidden, classes, num_layers=2, num_heads=1, kernel=kernel, alpha=0.5, dropout=0.0, use_bn=True,
                           use_residual=True, use_graph=False, use_weight=False).to(dev)
-        opt = torch.optim.Adam(model.parameters(), weight_decay=0.1, lr=5e-4)
+        if args.optimizer == "torch":
+            opt = torch.optim.Adam(model.parameters(), weight_decay=0.1, lr=5e-4)
+        else:
+            from adam_step import make_optimizer                      # scripts/adam_step.py
+            opt = make_optimizer(args.optimizer, model.parameters(), weight_decay=0.1, lr=5e-4)
         x = torch.randn(n, f_in, device=dev)
         y = torch.randint(0, classes, (n,), device=dev)
         train_idx = torch.randperm(n, device=dev)[: classes * 100]

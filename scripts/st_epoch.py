@@ -1,7 +1,7 @@
 """Epoch time of the `spatial-temporal` folder's training loop (main.py:86-121) on the drop-in, at the shapes of its three
 datasets with the scripts' configuration (hidden 4, two layers, no Wv, edge_attr as edge_weight):
 
-    python scripts/st_epoch.py [--epochs 3] [--cpu-port] [--reference]
+    python scripts/st_epoch.py [--epochs 3] [--cpu-port] [--reference] [--optimizer torch|fused|capturable|difformer]
 
   chickenpox  n = 20,   d = 4,  104 training snapshots (train_ratio 0.2 of 517), static graph, cumulative cost
   covid       n = 129,  d = 8,   50 snapshots, a new edge list per snapshot, cumulative cost
@@ -69,12 +69,16 @@ def epoch(model, snaps, opt, cumulative):
     return float(cost_tr)
 
 
-def run(cls, host, d, kernel, use_graph, cumulative, device, epochs):
+def run(cls, host, d, kernel, use_graph, cumulative, device, epochs, optimizer="torch"):
     torch.manual_seed(123)
     model = cls(d, 4, 1, num_layers=2, alpha=0.5, dropout=0.2, num_heads=1, kernel=kernel, use_bn=True, use_residual=True,
                 use_graph=use_graph, use_weight=False).to(device)
     model.reset_parameters()
-    opt = torch.optim.Adam(model.parameters(), lr=0.01)
+    if optimizer == "torch" or device.type != "cuda":
+        opt = torch.optim.Adam(model.parameters(), lr=0.01)
+    else:
+        from adam_step import make_optimizer                      # scripts/adam_step.py
+        opt = make_optimizer(optimizer, model.parameters(), lr=0.01)
     times = []
     for e in range(epochs + 1):
         snaps = [tuple(a.clone().to(device) for a in s) for s in host]     # snapshot.to(device)
@@ -95,6 +99,8 @@ def main():
     ap.add_argument("--reference", action="store_true")
     ap.add_argument("--no-gpu", action="store_true")
     ap.add_argument("--only", default="", help="run the datasets whose name contains this")
+    ap.add_argument("--optimizer", default="torch", help="torch (torch.optim.Adam, the default) | fused | capturable | difformer "
+                    "(difformer_amd.Adam); GPU runs only")
     args = ap.parse_args()
     shapes = [("chickenpox", 20, 4, 4, 104, False, False, True), ("covid", 129, 8, 12, 50, True, False, True),
               ("wikimath", 1068, 14, 10, 146, False, False, False), ("chickenpox-dense", 20, 4, 4, 104, False, True, True),
@@ -137,7 +143,7 @@ def main():
                 cells = []
                 for label, cls, device in impls:
                     ep = 1 if (device.type == "cpu" and n > 500) else args.epochs
-                    sec, cost = run(cls, host, d, kernel, use_graph, cumulative, device, ep)
+                    sec, cost = run(cls, host, d, kernel, use_graph, cumulative, device, ep, args.optimizer)
                     cells.append(f"{sec * 1e3:9.1f} ms ({sec / T * 1e6:7.0f} us/snap)")
                 print(f"{name:18s} {kernel:8s} {str(use_graph):6s} {T:4d}  " + "  ".join(f"{c:>28s}" for c in cells), flush=True)
 
