@@ -34,6 +34,9 @@ LOSS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "diffor
 # the optimiser library (C ABI: include/difformer_adam.h), loaded on first use by load_adam()
 ADAM_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_adam.so")
 ADAM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_adam.h"))
+# the graph read-out library (C ABI: include/difformer_readout.h), loaded on first use by load_readout()
+READOUT_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_readout.so")
+READOUT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_readout.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -167,6 +170,12 @@ ADAM_VERSION = _defines(_adam_code, "DIF_ADAM_VERSION")["DIF_ADAM_VERSION"]
 ADAM_CONSTANTS = _defines(_adam_code, r"DIF_ADAM_(?:MAX_TENSORS|CHUNK|TABLE_FIELDS|TICKET_BYTES)")   # launch geometry, table row, tickets
 ADAM_SIGNATURES = _prototypes(_adam_code)
 
+# ... and include/difformer_readout.h of the ninth's
+_readout_code = _read_header(READOUT_HEADER_PATH)
+READOUT_VERSION = _defines(_readout_code, "DIF_READOUT_VERSION")["DIF_READOUT_VERSION"]
+READOUT_CONSTANTS = _defines(_readout_code, r"DIF_READOUT_(?:ADD|MEAN|MAX|MAX_COLUMNS)")      # mode codes, the column limit
+READOUT_SIGNATURES = _prototypes(_readout_code)
+
 _lib = None
 _maps = None
 _edges = None
@@ -175,6 +184,7 @@ _slots = None
 _metrics = None
 _loss = None
 _adam = None
+_readout = None
 
 
 class DifformerHipError(RuntimeError):
@@ -301,6 +311,14 @@ def load_adam():
     return _adam
 
 
+def load_readout():
+    """Load libdifformer_readout.so once."""
+    global _readout
+    if _readout is None:
+        _readout = _load_side(READOUT_LIB_PATH, READOUT_SIGNATURES, "dif_readout_version", READOUT_VERSION)
+    return _readout
+
+
 def check_maps(rc, what):
     """check() for a call into libdifformer_maps.so: the message comes from that library."""
     if rc != 0:
@@ -347,6 +365,13 @@ def check_adam(rc, what):
     """check() for a call into libdifformer_adam.so: the message comes from that library."""
     if rc != 0:
         msg = load_adam().dif_adam_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
+
+
+def check_readout(rc, what):
+    """check() for a call into libdifformer_readout.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_readout().dif_readout_last_error()
         raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 

@@ -230,19 +230,20 @@ class HipBackend:
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
     def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False, slots=False, metrics=False, loss=False,
-              adam=False):
+              adam=False, readout=False):
         """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
         a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
         `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
         collection, operands on the current device -- adds nothing around the call.  maps / edges / knn / slots / metrics /
-        loss / adam: `symbol` is one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so
+        loss / adam / readout: `symbol` is one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so
         (include/difformer_edges.h) / libdifformer_knn.so (include/difformer_knn.h) / libdifformer_slots.so
         (include/difformer_slots.h) / libdifformer_metrics.so (include/difformer_metrics.h) / libdifformer_loss.so
-        (include/difformer_loss.h) / libdifformer_adam.so (include/difformer_adam.h), loaded on first use."""
+        (include/difformer_loss.h) / libdifformer_adam.so (include/difformer_adam.h) / libdifformer_readout.so
+        (include/difformer_readout.h), loaded on first use."""
         side = ((_lib.load_maps, _lib.check_maps) if maps else (_lib.load_edges, _lib.check_edges) if edges else
                 (_lib.load_knn, _lib.check_knn) if knn else (_lib.load_slots, _lib.check_slots) if slots else
                 (_lib.load_metrics, _lib.check_metrics) if metrics else (_lib.load_loss, _lib.check_loss) if loss else
-                (_lib.load_adam, _lib.check_adam) if adam else None)
+                (_lib.load_adam, _lib.check_adam) if adam else (_lib.load_readout, _lib.check_readout) if readout else None)
         fn = getattr(side[0]() if side else self.lib, symbol)
         index = dev.index
         if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
@@ -572,6 +573,54 @@ class HipBackend:
         symbol = ("dif_nll_log_softmax_bwd_" if kind == "nll" else "dif_bce_with_logits_bwd_") + sfx
         self._call(symbol, symbol, dev, *args, n, C, _ptr(record), _ptr(upstream), _ptr(grad), C, loss=True)
         return grad
+
+    # ---- graph read-out (libdifformer_readout.so) --------------------------------------------------
+    @staticmethod
+    def _readout_table(who, graph_ptr, dev):
+        if graph_ptr.dtype != torch.int32 or graph_ptr.dim() != 1 or graph_ptr.shape[0] < 1 or graph_ptr.device != dev:
+            raise ValueError(f"difformer_amd: {who} takes graph_ptr as int32 [B + 1] on {dev} (got {graph_ptr.dtype}, "
+                             f"{tuple(graph_ptr.shape)}, {graph_ptr.device})")
+        return graph_ptr.contiguous()
+
+    def readout_fwd(self, x, graph_ptr, mode):
+        """x [N, H] float32 or bfloat16 (a row-strided view is not copied), graph_ptr int32 [B + 1] as ops.BatchLayout makes it
+        (graph b = rows [graph_ptr[b], graph_ptr[b+1]), graph_ptr[B] == N), mode 'add' | 'mean' | 'max' -> [B, H] in x's dtype,
+        every element written (csrc/graph_readout.hip; arithmetic and edge semantics: include/difformer_readout.h)."""
+        dev = _require_device(x, graph_ptr)
+        _, sfx = _storage(x)
+        N, H = x.shape
+        graph_ptr = self._readout_table("readout_fwd", graph_ptr, dev)
+        B = graph_ptr.shape[0] - 1
+        x, ldx = _loss_rows(x, H)
+        out = torch.empty((B, H), dtype=x.dtype, device=dev)
+        symbol = "dif_readout_fwd_" + sfx
+        self._call(symbol, symbol, dev, _ptr(x), ldx, _ptr(graph_ptr), B, N, H, _lib.READOUT_CONSTANTS["DIF_READOUT_" + mode.upper()],
+                   _ptr(out), H, readout=True)
+        return out
+
+    def readout_bwd(self, grad_out, graph_ptr, mode, n_rows, x=None, pooled=None):
+        """grad_out [B, H] -> d / d x [n_rows, H] in grad_out's dtype, every element written once.  mode 'max' needs the
+        forward's x and its result `pooled`; the other modes read neither."""
+        dev = _require_device(grad_out, graph_ptr, x, pooled)
+        _, sfx = _storage(grad_out, x, pooled)
+        B, H = grad_out.shape
+        graph_ptr = self._readout_table("readout_bwd", graph_ptr, dev)
+        if graph_ptr.shape[0] != B + 1:
+            raise ValueError(f"difformer_amd: readout_bwd: grad_out has {B} rows for {graph_ptr.shape[0] - 1} graphs")
+        grad_out, ldgo = _loss_rows(grad_out, H)
+        ldx = ldp = 0
+        if mode == "max":
+            if x is None or pooled is None or tuple(x.shape) != (n_rows, H) or tuple(pooled.shape) != (B, H):
+                raise ValueError(f"difformer_amd: readout_bwd: mode 'max' needs x {(n_rows, H)} and pooled {(B, H)}")
+            x, ldx = _loss_rows(x, H)
+            pooled, ldp = _loss_rows(pooled, H)
+        else:
+            x = pooled = None
+        grad_x = torch.empty((n_rows, H), dtype=grad_out.dtype, device=dev)
+        symbol = "dif_readout_bwd_" + sfx
+        self._call(symbol, symbol, dev, _ptr(x), ldx, _ptr(pooled), ldp, _ptr(grad_out), ldgo, _ptr(graph_ptr), B, n_rows, H,
+                   _lib.READOUT_CONSTANTS["DIF_READOUT_" + mode.upper()], _ptr(grad_x), H, readout=True)
+        return grad_x
 
     # ---- attention on graph edges (libdifformer_edges.so) ----------------------------------------
     def edge_attention(self, q, k, scale, edge_index, mode):

@@ -97,6 +97,23 @@ __host__ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
     return static_cast<uint16_t>(c.u >> 16);
 }
 
+// float64 -> bfloat16 in ONE rounding to nearest even.  Through float32 the value is rounded twice; the two differ only where
+// the float32 lands exactly half-way between two bfloat16 values without being the float64 -- then the float64 decides.
+__device__ __forceinline__ uint16_t f64_to_bf16(double d) {
+    const float f = static_cast<float>(d);
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40u);      // NaN stays NaN
+    uint32_t up = u >> 16;
+    const uint32_t low = u & 0xffffu;
+    if (low > 0x8000u) {
+        up += 1;
+    } else if (low == 0x8000u) {
+        const double a = fabs(d), b = fabs(static_cast<double>(f));
+        if (a > b || (a == b && (up & 1u))) up += 1;
+    }
+    return static_cast<uint16_t>(up);
+}
+
 // A pointer the compiler could not prove global (computed from loaded indices inside a loop, rebuilt from an integer, read out of
 // a struct argument) is dereferenced with FLAT instructions: slower, and they count on the LDS counter too.  Every tensor this
 // library touches is device-global memory: say so where it matters.

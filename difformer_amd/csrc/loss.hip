@@ -62,24 +62,9 @@ static_assert(sizeof(Record) == DIF_LOSS_RECORD_BYTES, "the record of include/di
 __device__ __forceinline__ double widen(const float* p) { return static_cast<double>(*p); }
 __device__ __forceinline__ double widen(const dif::bf16* p) { return static_cast<double>(dif::bf16_to_f32(p->bits)); }
 
-// float64 -> bfloat16 in ONE rounding to nearest even.  Through float32 the value is rounded twice; the two differ only where
-// the float32 lands exactly half-way between two bfloat16 values without being the float64 -- then the float64 decides.
-__device__ __forceinline__ uint16_t f64_to_bf16(double d) {
-    const float f = static_cast<float>(d);
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40u);      // NaN stays NaN
-    uint32_t up = u >> 16;
-    const uint32_t low = u & 0xffffu;
-    if (low > 0x8000u) {
-        up += 1;
-    } else if (low == 0x8000u) {
-        const double a = fabs(d), b = fabs(static_cast<double>(f));
-        if (a > b || (a == b && (up & 1u))) up += 1;
-    }
-    return static_cast<uint16_t>(up);
-}
+// one rounding from float64 (dif::f64_to_bf16 does not go through float32's)
 __device__ __forceinline__ void store(float* p, double v) { *p = static_cast<float>(v); }
-__device__ __forceinline__ void store(dif::bf16* p, double v) { p->bits = f64_to_bf16(v); }
+__device__ __forceinline__ void store(dif::bf16* p, double v) { p->bits = dif::f64_to_bf16(v); }
 
 __device__ __forceinline__ int row_weight(const void* rows, int kind, int64_t r) {
     if (kind == DIF_LOSS_ROWS_WEIGHTS) {
