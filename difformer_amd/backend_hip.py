@@ -205,6 +205,23 @@ class _Timed:
         return self.ctx.__exit__(*exc) if self.ctx is not None else False
 
 
+SLICED_RECORDS_BIT = 1 << 18     # plan[0] of the sliced product: position records in front of `entries` (difformer_hip.h)
+
+
+def sliced_run_plan(plan, positions):
+    """The plan record of a sliced format with (positions) or without the bit that announces its position records: a
+    private ctypes copy, the caller's plan stays as it is."""
+    v = [int(x) for x in plan]
+    v[0] = (v[0] | SLICED_RECORDS_BIT) if positions else (v[0] & ~SLICED_RECORDS_BIT)
+    return (ctypes.c_int32 * 8)(*v)
+
+
+def sliced_record_elems(plan):
+    """int16 elements the position records take in front of the entry blocks: 8 bytes for each of the 64 positions of the
+    plan's G slots when plan[0] announces them, else 0.  A multiple of 256 elements, so the blocks keep their alignment."""
+    return int(plan[2]) * 64 * 4 if int(plan[0]) & SLICED_RECORDS_BIT else 0
+
+
 class HipBackend:
     has_tiny = True          # the whole-model kernels for tiny graphs (tiny.py; csrc/tiny_model.hip) are in this library
     name = "hip"
@@ -1177,14 +1194,19 @@ class HipBackend:
         rc = self.lib.dif_sliced_plan(int(n_src), int(n_rows), int(F), plan)
         return plan if rc == 0 else None
 
+    sliced_run_plan = staticmethod(sliced_run_plan)
+
     def sliced_build(self, rowptr, blkptr, src, n_src, nnz, row_begin, n_rows, F, plan, order=None, parts=None, n_pos=None,
-                     quad_cap=1):
+                     quad_cap=1, positions=False):
         """-> (entries uint16 [512 * n_blocks], table int32) or None when a (row position, tile) group exceeds the 16-bit
         counters.  order: the shard's rows by descending degree (row_order) for skewed graphs, None = natural order;
         parts (uint16 [n_pos], with order int32 [n_pos]): hub rows split into lock-step parts (include/difformer_hip.h,
         "row positions"); plan = sliced_plan(n_src, n_pos, F).  quad_cap: lanes of a hardware lane group that may read
         one bank quad in a step (1 = strict, conflict-free schedule; 2 = packed); it goes to the two build calls in bits
         16-17 of plan[0] of a private copy of the plan (include/difformer_hip.h), the caller's plan stays as it is.
+        positions: the format carries one 8-byte record {row, deg^-1/2} per row position for the product's epilogue (bit
+        18 of that private plan[0]).  The records lie in FRONT of the blocks in one allocation (sliced_record_elems of
+        the plan); `entries` is the view behind them, so it has the same shape and content with and without records.
         Two host syncs (status, block count): cold path, once per (graph, shard, F)."""
         dev = _require_device(rowptr, blkptr, src, order, parts)
         n_pos = int(n_rows) if n_pos is None else int(n_pos)
@@ -1192,6 +1214,7 @@ class HipBackend:
         if not 1 <= int(quad_cap) <= 4:
             raise ValueError(f"difformer_amd: quad_cap={quad_cap!r}: expected 1 (strict) or 2 (packed)")
         plan = (ctypes.c_int32 * 8)(slices | (int(quad_cap) - 1) << 16, panels, G, PW, W, R, T, NT)
+        emit_plan = sliced_run_plan(plan, positions)         # only dif_sliced_emit (and the product) take the records bit
         i32 = dict(dtype=torch.int32, device=dev)
         srt = torch.empty(max(int(nnz), 1), dtype=torch.int16, device=dev)
         counts = torch.empty(n_pos * NT * 32, dtype=torch.uint8, device=dev)
@@ -1204,9 +1227,12 @@ class HipBackend:
         bad, n_blocks = (int(v) for v in torch.stack([status[0], table[-1]]).tolist())
         if bad:
             return None
-        entries = torch.empty(512 * max(n_blocks, 1), dtype=torch.int16, device=dev)
+        head = sliced_record_elems(emit_plan)
+        entries = torch.empty(head + 512 * max(n_blocks, 1), dtype=torch.int16, device=dev)
+        if head:
+            entries = entries[head:]
         self._call("dif_sliced_emit", "dif_sliced_emit", dev, _ptr(rowptr), _ptr(blkptr), int(n_src), int(row_begin),
-                   int(n_rows), int(F), plan, _ptr(order), _ptr(parts), n_pos, _ptr(srt), _ptr(counts), _ptr(table),
+                   int(n_rows), int(F), emit_plan, _ptr(order), _ptr(parts), n_pos, _ptr(srt), _ptr(counts), _ptr(table),
                    max(n_blocks, 1), _ptr(entries))
         return entries, table
 
@@ -1246,7 +1272,12 @@ class HipBackend:
         n_pos = int(n_rows) if sl.n_pos is None else int(sl.n_pos)
         ws_bytes = self.lib.dif_sliced_spmm_workspace_bytes(int(n_src), n_pos, int(F))   # > 0: a row shard (source splits)
         ws = _workspace(ws_bytes, dev, or_none=True)
-        self._call("dif_sliced_spmm_f32", "dif_sliced_spmm_f32", dev, _ptr(sl.entries), _ptr(sl.table), sl.plan, _ptr(ys),
+        plan = sl.plan
+        if getattr(sl, "positions", False):             # the format was built with position records: say so in plan[0]
+            plan = sl.run_plan
+            if sl.entries.storage_offset() < sliced_record_elems(plan):
+                raise ValueError("difformer_amd: this sliced format has lost the position records in front of its entries")
+        self._call("dif_sliced_spmm_f32", "dif_sliced_spmm_f32", dev, _ptr(sl.entries), _ptr(sl.table), plan, _ptr(ys),
                    _ptr(rowptr), _ptr(dinv), _ptr(sl.order), _ptr(sl.parts), n_pos, int(n_src), int(row_begin), int(n_rows),
                    int(F), _ptr(attn), lda, float(attn_scale), float(gcn_scale), _ptr(out), F, _ptr(ws), ws_bytes)
         return out

@@ -438,6 +438,14 @@ __global__ __launch_bounds__(kColorThreads) void sliced_color_kernel(int64_t n_p
 // fit (hub rows) read global memory directly.
 constexpr int kFillStage = 4096;                 // entries of one slot in LDS (8 KiB per wave)
 
+// One record per row position (8 bytes, position order, the G * 64 of them END where `entries` begins): the row of
+// the position inside the shard (-1: empty, or beyond n_pos) and its scale deg^-1/2 = dinv_of(rowptr, row_begin + row).
+// Written once per format by sliced_fill_kernel (the waves of tile 0) when the plan record asks for them
+// (kPlanRecordsBit), so that a (wave, round) of the product's epilogue reads one coalesced 512-byte line instead of
+// order[pos] and two divergent gathers of rowptr, and the 16 slice-workgroups of a panel no longer take the same divide
+// and square root 16 times.
+struct alignas(8) PosRecord { int32_t row; float scale; };
+
 template <bool STAGED>
 __device__ __forceinline__ void fill_blocks(const uint16_t* __restrict__ mine, const uint16_t* stage, Counts next,
                                             const int32_t* __restrict__ tb, int R, int j, int nbj, int64_t blk0, int grp,
@@ -478,7 +486,7 @@ __global__ __launch_bounds__(256) void sliced_fill_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ blkptr, int64_t n_src, int64_t row_begin,
     int64_t n_pos, const int32_t* __restrict__ order, const uint16_t* __restrict__ parts, Plan pl,
     const uint16_t* __restrict__ srt, const uint4* __restrict__ cnt, const int32_t* __restrict__ tab,
-    uint4* __restrict__ ell) {
+    uint4* __restrict__ ell, PosRecord* __restrict__ rec) {
     __shared__ uint16_t stage_s[4][kFillStage + 8];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -493,12 +501,17 @@ __global__ __launch_bounds__(256) void sliced_fill_kernel(
     const int32_t* tb = tab + ((static_cast<int64_t>(p) * pl.NT + t) * pl.W + w) * (pl.R + 1);
     const int64_t blk0 = tb[0];
     const int nbj = tb[1 + j];
+    const int64_t pos = g * 64 + lane;
+    if (rec && t == 0) {                           // the slot's position records (PosRecord), once per format
+        int64_t lrow = -1;
+        if (pos < n_pos) lrow = order ? order[pos] : pos;
+        rec[pos] = PosRecord{static_cast<int32_t>(lrow), lrow >= 0 ? dinv_of(rowptr, row_begin + lrow) : 0.f};
+    }
     if (nbj == 0) return;
     int inv = 0;                                   // lane = kLaneOf[inv]: group inv >> 4, index inv & 15
 #pragma unroll
     for (int k = 0; k < 64; ++k) inv = (kLaneOf[k] == lane) ? k : inv;
     const int grp = inv >> 4, i = inv & 15;
-    const int64_t pos = g * 64 + lane;
     Counts next = {{0, 0, 0, 0}};
     int32_t e0 = 0, e1 = 0;
     if (pos < n_pos) {
@@ -643,6 +656,7 @@ struct Epilogue {
     float* out;
     int64_t ldo;
     f32x4* partial;        // S > 1: [S][slices][G * 64] raw sums of the splits, finished by sliced_combine_kernel
+    const PosRecord* rec;  // the format's position records; NULL: it has none, or a caller's dinv (the epilogue gathers)
 };
 
 // one block of a round: eight entries (four packed dwords), 16-bit row number -> LDS byte address with one SDWA shift
@@ -713,9 +727,19 @@ struct Phases<0, NR> {
 
 // The sum of one row position (all 64 lanes of a slot call this together): parts of a split row are added up by
 // part 0, then the row is scaled, combined with the attention branch and stored.
-__device__ __forceinline__ void finish_position(const Epilogue& ep, int64_t pos, int slice, f32x4 acc) {
+// rec: the format's position records (pos < G * 64 always), or NULL -- then the row comes from `order` and its scale from
+// the caller's dinv or the row lengths, as before the format had records.
+__device__ __forceinline__ void finish_position(const Epilogue& ep, const PosRecord* __restrict__ rec, int64_t pos, int slice,
+                                                f32x4 acc) {
     int64_t lrow = -1;
-    if (pos < ep.n_pos) lrow = ep.order ? ep.order[pos] : pos;
+    float scale = 0.f;
+    if (rec) {
+        const PosRecord r = rec[pos];
+        lrow = r.row;
+        scale = r.scale;
+    } else if (pos < ep.n_pos) {
+        lrow = ep.order ? ep.order[pos] : pos;
+    }
     f32x4 sum = acc;
     if (ep.parts) {
         // the parts of a split row sit in consecutive lanes of this slot: part 0 adds them up in part order
@@ -733,7 +757,8 @@ __device__ __forceinline__ void finish_position(const Epilogue& ep, int64_t pos,
     }
     if (lrow >= 0) {
         const int64_t row = ep.row_begin + lrow;
-        f32x4 o = sum * (ep.gcn_scale * (ep.dinv ? ep.dinv[row] : dinv_of(ep.rowptr, row)));
+        if (!rec) scale = ep.dinv ? ep.dinv[row] : dinv_of(ep.rowptr, row);
+        f32x4 o = sum * (ep.gcn_scale * scale);
         if (ep.attn) o += ep.attn_scale * *reinterpret_cast<const f32x4*>(ep.attn + lrow * ep.lda + slice * 4);
         *reinterpret_cast<f32x4*>(ep.out + lrow * ep.ldo + slice * 4) = o;
     }
@@ -749,21 +774,42 @@ __device__ __forceinline__ void sweep(f32x4* tile, const uint4* __restrict__ ell
 #pragma unroll
     for (int j = 0; j < NA; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int ntl = pl.NT / pl.S;                                             // this split's tiles: [z * ntl, (z + 1) * ntl)
-    for (int tt = 0; tt < ntl; ++tt) {
-        int t = tt + t0;                                                      // XCDs start on different tiles (t0)
+    auto tile_of = [&](int tt) {                                              // XCDs start on different tiles (t0)
+        int t = tt + t0;
         if (t >= ntl) t -= ntl;
-        t += z * ntl;
+        return t + z * ntl;
+    };
+    // The table row of a tile {first block, blocks per round} is read one tile AHEAD, with scalar loads at the top of
+    // the tile before: a tile no longer starts with a dependent read (table row -> entry loads -> tile loads) whose
+    // latency the last wave into the barrier pays in full.
+    int first = 0, nbn[NA];
+#pragma unroll
+    for (int j = 0; j < NA; ++j) nbn[j] = 0;
+    int t = tile_of(0);
+    if (NR > 0) {
+        const int32_t* tr = tabw + static_cast<int64_t>(t) * tab_stride;
+        first = __builtin_amdgcn_readfirstlane(tr[0]);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) nbn[j] = __builtin_amdgcn_readfirstlane(tr[1 + j]);
+    }
+    for (int tt = 0; tt < ntl; ++tt) {
         uint4 e[NA];
         int nb[NA];
         const uint4* cur = ell;
         if (NR > 0) {
-            const int32_t* tr = tabw + static_cast<int64_t>(t) * tab_stride;
-            cur = ell + static_cast<int64_t>(__builtin_amdgcn_readfirstlane(tr[0])) * 64 + lane;
+            cur = ell + static_cast<int64_t>(first) * 64 + lane;
 #pragma unroll
             for (int j = 0; j < NR; ++j) {
-                nb[j] = __builtin_amdgcn_readfirstlane(tr[1 + j]);
+                nb[j] = nbn[j];
                 e[j] = *((nb[j] > 0) ? cur + j * 64 : ell);                  // in flight across the tile load
             }
+        }
+        const int tnext = tile_of(tt + 1 < ntl ? tt + 1 : tt);               // the last tile reads nothing ahead
+        if (NR > 0 && tt + 1 < ntl) {
+            const int32_t* tr = tabw + static_cast<int64_t>(tnext) * tab_stride;
+            first = __builtin_amdgcn_readfirstlane(tr[0]);
+#pragma unroll
+            for (int j = 0; j < NR; ++j) nbn[j] = __builtin_amdgcn_readfirstlane(tr[1 + j]);
         }
         {
             // The tile's first loads are issued BEFORE the barrier (they land in registers, not in LDS), so their latency
@@ -805,12 +851,18 @@ __device__ __forceinline__ void sweep(f32x4* tile, const uint4* __restrict__ ell
             int k = 0;
             Phases<NR, NA>::run(tile, k, cur, e, acc, nb);
         }
+        t = tnext;
+    }
+    if (pl.S == 1 && ep.rec) {               // its own loop: the record loads of all the rounds go out together
+#pragma unroll
+        for (int j = 0; j < NR; ++j) finish_position(ep, ep.rec, slot_of(j, pw, pl.PW) * 64 + lane, slice, acc[j]);
+        return;
     }
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
         const int64_t pos = slot_of(j, pw, pl.PW) * 64 + lane;
         if (pl.S > 1) ep.partial[(static_cast<int64_t>(z) * pl.slices + slice) * pl.G * 64 + pos] = acc[j];
-        else finish_position(ep, pos, slice, acc[j]);
+        else finish_position(ep, nullptr, pos, slice, acc[j]);
     }
 }
 
@@ -860,7 +912,7 @@ __global__ __launch_bounds__(256) void sliced_combine_kernel(Plan pl, Epilogue e
 #pragma unroll
     for (int z = 1; z < kMaxSplits; ++z)
         if (z < pl.S) sum += v[z];
-    finish_position(ep, pos, slice, sum);
+    finish_position(ep, ep.rec, pos, slice, sum);
 }
 
 template <int R>
@@ -883,17 +935,22 @@ int check_positions(const int32_t* row_order, const uint16_t* parts, int64_t n_r
 
 // The schedule rides in the plan record: plan[0] = F / 4 (<= 256) in its low 16 bits and the quad capacity - 1 in bits
 // 16-17 (0 as dif_sliced_plan writes it: the strict schedule).  Only the two build calls look at the capacity.
-constexpr int32_t kPlanSlicesMask = 0xffff, kPlanCapMask = 0x30000;
+// Bit 18 says that the G * 64 position records (PosRecord, 8 bytes each) lie in FRONT of `entries`, in the same
+// allocation and ending where `entries` begins (G * 512 bytes: the alignment of `entries` is kept): dif_sliced_emit writes
+// them, dif_sliced_spmm_f32 reads them (unless the caller brings a dinv vector); every other call takes the plan without
+// the bit (dif_sliced_measure has nothing to do with the records and reports it as a mismatch).
+constexpr int32_t kPlanSlicesMask = 0xffff, kPlanCapMask = 0x30000, kPlanRecordsBit = 0x40000;
 int plan_quad_cap(const int32_t* plan) { return ((plan[0] & kPlanCapMask) >> 16) + 1; }
+bool plan_has_records(const int32_t* plan) { return (plan[0] & kPlanRecordsBit) != 0; }
 
-int check_plan(const int32_t* plan, int64_t n_src, int64_t n_rows, int F, Plan& pl) {
+int check_plan(const int32_t* plan, int64_t n_src, int64_t n_rows, int F, Plan& pl, int32_t flags = kPlanCapMask) {
     if (!plan) return dif::fail(DIF_E_BADARG, "dif_sliced: plan is null");
     Plan want;
     const int rc = make_plan(n_src, n_rows, F, want);
     if (rc) return dif::fail(rc, "dif_sliced: shape not covered (n_src=%lld, n_rows=%lld, F=%d)",
                              static_cast<long long>(n_src), static_cast<long long>(n_rows), F);
     pl = Plan{plan[0] & kPlanSlicesMask, plan[1], plan[2], plan[3], plan[4], plan[5], plan[6], plan[7], want.S};
-    if ((plan[0] & ~(kPlanSlicesMask | kPlanCapMask)) != 0) pl.slices = -1;      // unknown bits: reported as a mismatch below
+    if ((plan[0] & ~(kPlanSlicesMask | flags)) != 0) pl.slices = -1;      // unknown bits: reported as a mismatch below
     if (pl.slices != want.slices || pl.panels != want.panels || pl.G != want.G || pl.PW != want.PW || pl.W != want.W ||
         pl.R != want.R || pl.T != want.T || pl.NT != want.NT)
         return dif::fail(DIF_E_BADARG, "dif_sliced: plan does not match dif_sliced_plan(n_src, n_rows, F)");
@@ -953,7 +1010,7 @@ extern "C" int dif_sliced_emit(const int32_t* rowptr, const int32_t* blkptr, int
                                int64_t n_blocks, uint16_t* entries, dif_stream_t stream) {
     Plan pl;
     if (int rc = check_positions(row_order, parts, n_rows, n_pos, "dif_sliced_emit")) return rc;
-    if (int rc = check_plan(plan, n_src, n_pos, F, pl)) return rc;
+    if (int rc = check_plan(plan, n_src, n_pos, F, pl, kPlanCapMask | kPlanRecordsBit)) return rc;
     const int quad_cap = plan_quad_cap(plan);
     DIF_REQUIRE(quad_cap <= 2, DIF_E_BADARG, "dif_sliced_emit: the plan's quad capacity must be 1 (strict) or 2 (packed)");
     DIF_REQUIRE(rowptr && sorted && counts && table && entries && n_blocks >= 1, DIF_E_BADARG, "dif_sliced_emit: null pointer");
@@ -966,9 +1023,10 @@ extern "C" int dif_sliced_emit(const int32_t* rowptr, const int32_t* blkptr, int
                              dif::grid_of((n_hw + kColorThreads - 1) / kColorThreads), dim3(kColorThreads), 0, st, n_pos, pl,
                              quad_cap, static_cast<const uint4*>(counts), nullptr, table, entries)) return rc;
     const int64_t n_st = static_cast<int64_t>(pl.G) * pl.NT;                 // one wave per (slot, tile)
+    PosRecord* rec = plan_has_records(plan) ? reinterpret_cast<PosRecord*>(entries) - static_cast<int64_t>(pl.G) * 64 : nullptr;
     return dif::launch("sliced_fill_kernel", sliced_fill_kernel, dif::grid_of((n_st + 3) / 4), dim3(256), 0, st, rowptr, blkptr,
                        n_src, row_begin, n_pos, row_order, parts, pl, sorted, static_cast<const uint4*>(counts), table,
-                       reinterpret_cast<uint4*>(entries));
+                       reinterpret_cast<uint4*>(entries), rec);
 }
 
 extern "C" int dif_sliced_prescale_f32(const float* x, int64_t ldx, const int32_t* rowptr, const float* dinv, int64_t n_src,
@@ -993,7 +1051,7 @@ extern "C" int dif_sliced_spmm_f32(const uint16_t* entries, const int32_t* table
                                    int64_t ws_bytes, dif_stream_t stream) {
     Plan pl;
     if (int rc = check_positions(row_order, parts, n_rows, n_pos, "dif_sliced_spmm")) return rc;
-    if (int rc = check_plan(plan, n_src, n_pos, F, pl)) return rc;
+    if (int rc = check_plan(plan, n_src, n_pos, F, pl, kPlanCapMask | kPlanRecordsBit)) return rc;
     const int64_t ws_need = pl.S > 1 ? static_cast<int64_t>(pl.S) * pl.slices * pl.G * 64 * 16 : 0;
     DIF_REQUIRE(ws_need == 0 || (ws && ws_bytes >= ws_need && dif::aligned16(ws)), DIF_E_BADARG,
                 "dif_sliced_spmm: a row shard's product needs dif_sliced_spmm_workspace_bytes() of 16-byte aligned workspace");
@@ -1004,9 +1062,12 @@ extern "C" int dif_sliced_spmm_f32(const uint16_t* entries, const int32_t* table
     DIF_REQUIRE(dif::aligned16(entries) && dif::aligned16(ys), DIF_E_BADARG, "dif_sliced_spmm: entries / ys must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t npad = static_cast<int64_t>(pl.T) * pl.NT;
-    const Epilogue ep = {rowptr, dinv, row_order, parts, row_begin, n_pos, attn, lda, attn_scale, gcn_scale, out, ldo,
-                         static_cast<f32x4*>(ws)};
     const uint4* e4 = reinterpret_cast<const uint4*>(entries);
+    // a caller's dinv (the adjoint product) keeps the gathering epilogue: the records hold the scale of the row lengths
+    const PosRecord* rec = (plan_has_records(plan) && !dinv)
+                               ? reinterpret_cast<const PosRecord*>(entries) - static_cast<int64_t>(pl.G) * 64 : nullptr;
+    const Epilogue ep = {rowptr, dinv, row_order, parts, row_begin, n_pos, attn, lda, attn_scale, gcn_scale, out, ldo,
+                         static_cast<f32x4*>(ws), rec};
     const f32x4* y4 = reinterpret_cast<const f32x4*>(ys);
     return dif::with_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(
         pl.R, [&](auto R) { return launch_sweep<R>(st, e4, table, y4, npad, pl, ep); },

@@ -226,16 +226,29 @@ def packed_slot_order(rowptr, blkptr, n_src, NT, row_begin, n_rows):
     return torch.argsort(key, stable=True).to(torch.int32)
 
 
+# DIFFORMER_SLICED_POSITIONS = 1 (default): the format carries one 8-byte record {row, deg^-1/2} per row position, written
+# by the cold build, and the product's epilogue reads it as one coalesced line per (wave, round) instead of gathering
+# rowptr and taking the divide and square root again in each of the 16 slice-workgroups of a panel.
+# 0: no records, the gathering epilogue -- the same results bit for bit.
+def sliced_positions():
+    mode = os.environ.get("DIFFORMER_SLICED_POSITIONS", "1").strip() or "1"
+    if mode not in ("0", "1"):
+        raise ValueError(f"DIFFORMER_SLICED_POSITIONS={mode!r}: expected 0 or 1")
+    return mode == "1"
+
+
 class SlicedAdjacency:
     """Entry blocks + table + geometry of the feature-sliced product (include/difformer_hip.h, dif_sliced_*).
     order: rows by descending degree (skewed graphs) or by tile profile (packed schedule); parts / n_pos: hub rows split
     into lock-step parts ("row positions" in the header) -- then order has n_pos entries (-1 = padding) and plan is the
-    geometry of n_pos positions; quad_cap: 1 = strict schedule, 2 = packed.
-    The slice-major source copy is written with the same plan (its tiling)."""
+    geometry of n_pos positions; quad_cap: 1 = strict schedule, 2 = packed; positions: the allocation of `entries`
+    holds the position records in front of them (backend sliced_build) and run_plan, the plan the product is called
+    with, says so.  The slice-major source copy is written with the same plan (its tiling)."""
 
-    def __init__(self, plan, entries, table, order=None, parts=None, n_pos=None, quad_cap=1):
+    def __init__(self, plan, entries, table, order=None, parts=None, n_pos=None, quad_cap=1, positions=False):
         self.plan, self.entries, self.table, self.order = plan, entries, table, order
-        self.parts, self.n_pos, self.quad_cap = parts, n_pos, int(quad_cap)
+        self.parts, self.n_pos, self.quad_cap, self.positions = parts, n_pos, int(quad_cap), bool(positions)
+        self.run_plan = get_backend().sliced_run_plan(plan, True) if self.positions else plan
 
 
 def split_positions(deg_sorted, order, cap, max_parts=SLICED_MAX_PARTS):
@@ -360,11 +373,13 @@ class GraphCSR:
         elif NT <= SLICED_PACKED_MAX_TILES and (mode == "packed" or (mode == "auto" and total >= SLICED_PACKED_MIN_ENTRIES)):
             order = packed_order(be, self.rowptr, self.blkptr, self.num_nodes, NT, row_begin, n_rows, plan)
             quad_cap = 2
+        # the records hold deg^-1/2 of this CSR's row lengths: not for an adjoint CSR, whose products bring the forward dinv
+        positions = sliced_positions() and self.dinv is None
         built = be.sliced_build(self.rowptr, self.blkptr, self.src, self.num_nodes, self.nnz, row_begin, n_rows, F, plan, order,
-                                parts, n_pos, quad_cap)
+                                parts, n_pos, quad_cap, positions)
         if built is None:
             return None
-        return SlicedAdjacency(plan, built[0], built[1], order, parts, n_pos, quad_cap)
+        return SlicedAdjacency(plan, built[0], built[1], order, parts, n_pos, quad_cap, positions)
 
     def row_sums(self):
         """A_hat 1 (float32 [N]): what the bias of the value projection turns into under the aggregation,

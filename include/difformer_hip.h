@@ -325,6 +325,14 @@ int dif_simple_layer_f32(const float* x, int64_t ldx, int64_t n_rows, int C, int
  *                       one slot (near-uniform degrees).  dif_sliced_measure and dif_sliced_emit of one build take the
  *                       same value; larger capacities: DIF_E_BADARG.  dif_sliced_prescale_f32 and dif_sliced_spmm_f32
  *                       ignore the bits (the format is the same); every other call takes the plan without them.
+ *   position records    Bit 18 of plan[0] says that the format carries one 8-byte record per row position, {int32 row inside
+ *                       the shard (-1: empty position, or beyond n_pos), float deg^-1/2 of that row from the row lengths of
+ *                       `rowptr`}, for all 64 positions of the G slots, in position order.  The G * 512 bytes lie in FRONT
+ *                       of `entries`, in the same allocation, and end where `entries` begins (so `entries` itself is the
+ *                       same with and without them).  dif_sliced_emit with the bit writes them; dif_sliced_spmm_f32 with
+ *                       the bit and dinv = NULL reads one record per (position, slice) instead of row_order, two elements
+ *                       of rowptr and a divide and square root -- the same values, bit for bit.  With a caller's dinv
+ *                       the product ignores the bit.  dif_sliced_measure and every other call take the plan without it.
  *   dif_sliced_prescale_f32  ys float[F/4][T*NT][4] = deg^-1/2 (0 for a node without incoming entries, :74) times x,
  *                       slice-major; x holds all n_src rows.
  *   dif_sliced_spmm_f32 out[r,:] = gcn_scale * deg[r]^-1/2 * sum_e ys[src_e] (+ attn_scale * attn[r,:]) for the n_rows
