@@ -12,6 +12,7 @@ import os
 import torch
 
 from . import _lib
+from .sliced import SlicedPlan
 from .tensor_cache import MISS, TensorCache
 
 
@@ -141,7 +142,7 @@ def _loss_rows(t, C):
 
 def _slice_major(F, plan, dev):
     """ys [F/4, T*NT, 4]: the slice-major copy of [n, F] rows that sliced_spmm reads (plan: sliced_plan's geometry)."""
-    return torch.empty((F // 4, int(plan[6]) * int(plan[7]), 4), dtype=torch.float32, device=dev)
+    return torch.empty((F // 4, plan.T * plan.NT, 4), dtype=torch.float32, device=dev)
 
 
 def _check_edge_index(edge_index):
@@ -203,23 +204,6 @@ class _Timed:
             end.record(torch.cuda.current_stream(self.dev))
             self.rec.setdefault(self.name, []).append((self.start, end))
         return self.ctx.__exit__(*exc) if self.ctx is not None else False
-
-
-SLICED_RECORDS_BIT = 1 << 18     # plan[0] of the sliced product: position records in front of `entries` (difformer_hip.h)
-
-
-def sliced_run_plan(plan, positions):
-    """The plan record of a sliced format with (positions) or without the bit that announces its position records: a
-    private ctypes copy, the caller's plan stays as it is."""
-    v = [int(x) for x in plan]
-    v[0] = (v[0] | SLICED_RECORDS_BIT) if positions else (v[0] & ~SLICED_RECORDS_BIT)
-    return (ctypes.c_int32 * 8)(*v)
-
-
-def sliced_record_elems(plan):
-    """int16 elements the position records take in front of the entry blocks: 8 bytes for each of the 64 positions of the
-    plan's G slots when plan[0] announces them, else 0.  A multiple of 256 elements, so the blocks keep their alignment."""
-    return int(plan[2]) * 64 * 4 if int(plan[0]) & SLICED_RECORDS_BIT else 0
 
 
 class HipBackend:
@@ -1189,37 +1173,30 @@ class HipBackend:
 
     # ---- a3, dense unweighted graphs: feature-sliced product with LDS-staged sources (csrc/gcn_sliced.hip) ----------
     def sliced_plan(self, n_src, n_rows, F):
-        """int32[8] geometry (ctypes array) or None when the shape is not covered."""
-        plan = (ctypes.c_int32 * 8)()
+        """The geometry (sliced.SlicedPlan, an int32[8] ctypes array) or None when the shape is not covered."""
+        plan = SlicedPlan()
         rc = self.lib.dif_sliced_plan(int(n_src), int(n_rows), int(F), plan)
         return plan if rc == 0 else None
-
-    sliced_run_plan = staticmethod(sliced_run_plan)
 
     def sliced_build(self, rowptr, blkptr, src, n_src, nnz, row_begin, n_rows, F, plan, order=None, parts=None, n_pos=None,
                      quad_cap=1, positions=False):
         """-> (entries uint16 [512 * n_blocks], table int32) or None when a (row position, tile) group exceeds the 16-bit
-        counters.  order: the shard's rows by descending degree (row_order) for skewed graphs, None = natural order;
-        parts (uint16 [n_pos], with order int32 [n_pos]): hub rows split into lock-step parts (include/difformer_hip.h,
-        "row positions"); plan = sliced_plan(n_src, n_pos, F).  quad_cap: lanes of a hardware lane group that may read
-        one bank quad in a step (1 = strict, conflict-free schedule; 2 = packed); it goes to the two build calls in bits
-        16-17 of plan[0] of a private copy of the plan (include/difformer_hip.h), the caller's plan stays as it is.
-        positions: the format carries one 8-byte record {row, deg^-1/2} per row position for the product's epilogue (bit
-        18 of that private plan[0]).  The records lie in FRONT of the blocks in one allocation (sliced_record_elems of
-        the plan); `entries` is the view behind them, so it has the same shape and content with and without records.
+        counters.  order (int32), parts (uint16), n_pos, quad_cap, positions: as sliced.SlicedAdjacency holds them; plan =
+        sliced_plan(n_src, n_pos, F).  quad_cap (1 = strict, conflict-free schedule; 2 = packed) and positions (one 8-byte
+        record {row, deg^-1/2} per row position for the product's epilogue) go to the two build calls in flagged copies of
+        the plan (sliced.SlicedPlan), the caller's plan stays as it is.  The records lie in FRONT of the blocks in one
+        allocation; `entries` is the view behind them, so it has the same shape and content with and without records.
         Two host syncs (status, block count): cold path, once per (graph, shard, F)."""
         dev = _require_device(rowptr, blkptr, src, order, parts)
         n_pos = int(n_rows) if n_pos is None else int(n_pos)
-        slices, panels, G, PW, W, R, T, NT = (int(v) for v in plan)
-        if not 1 <= int(quad_cap) <= 4:
-            raise ValueError(f"difformer_amd: quad_cap={quad_cap!r}: expected 1 (strict) or 2 (packed)")
-        plan = (ctypes.c_int32 * 8)(slices | (int(quad_cap) - 1) << 16, panels, G, PW, W, R, T, NT)
-        emit_plan = sliced_run_plan(plan, positions)         # only dif_sliced_emit (and the product) take the records bit
+        G, NT = plan.G, plan.NT
+        plan = plan.with_capacity(quad_cap)
+        emit_plan = plan.with_records(positions)             # only dif_sliced_emit (and the product) take the records bit
         i32 = dict(dtype=torch.int32, device=dev)
         srt = torch.empty(max(int(nnz), 1), dtype=torch.int16, device=dev)
         counts = torch.empty(n_pos * NT * 32, dtype=torch.uint8, device=dev)
         lengths = torch.empty(G * NT * 4, **i32)
-        table = torch.empty((R + 1) * panels * NT * W + 1, **i32)
+        table = torch.empty((plan.R + 1) * plan.panels * NT * plan.W + 1, **i32)
         status = torch.empty(1, **i32)
         self._call("dif_sliced_measure", "dif_sliced_measure", dev, _ptr(rowptr), _ptr(blkptr), _ptr(src), int(n_src),
                    int(nnz), int(row_begin), int(n_rows), int(F), plan, _ptr(order), _ptr(parts), n_pos, _ptr(srt),
@@ -1227,7 +1204,7 @@ class HipBackend:
         bad, n_blocks = (int(v) for v in torch.stack([status[0], table[-1]]).tolist())
         if bad:
             return None
-        head = sliced_record_elems(emit_plan)
+        head = emit_plan.record_elems
         entries = torch.empty(head + 512 * max(n_blocks, 1), dtype=torch.int16, device=dev)
         if head:
             entries = entries[head:]
@@ -1264,7 +1241,7 @@ class HipBackend:
         return ys
 
     def sliced_spmm(self, sl, ys, rowptr, n_src, row_begin, n_rows, F, attn=None, attn_scale=1.0, gcn_scale=1.0, dinv=None):
-        """sl: the format (ops.SlicedAdjacency: entries, table, plan, order, parts, n_pos) built for these rows."""
+        """sl: the format (sliced.SlicedAdjacency: entries, table, run_plan, order, parts, n_pos) built for these rows."""
         dev = _require_device(sl.entries, sl.table, ys, rowptr, attn, sl.order, sl.parts, dinv)
         _all_f32(attn=attn)
         attn, lda = _rows(attn, F, align=True)
@@ -1272,12 +1249,9 @@ class HipBackend:
         n_pos = int(n_rows) if sl.n_pos is None else int(sl.n_pos)
         ws_bytes = self.lib.dif_sliced_spmm_workspace_bytes(int(n_src), n_pos, int(F))   # > 0: a row shard (source splits)
         ws = _workspace(ws_bytes, dev, or_none=True)
-        plan = sl.plan
-        if getattr(sl, "positions", False):             # the format was built with position records: say so in plan[0]
-            plan = sl.run_plan
-            if sl.entries.storage_offset() < sliced_record_elems(plan):
-                raise ValueError("difformer_amd: this sliced format has lost the position records in front of its entries")
-        self._call("dif_sliced_spmm_f32", "dif_sliced_spmm_f32", dev, _ptr(sl.entries), _ptr(sl.table), plan, _ptr(ys),
+        if sl.entries.storage_offset() < sl.run_plan.record_elems:      # (0 for a format built without position records)
+            raise ValueError("difformer_amd: this sliced format has lost the position records in front of its entries")
+        self._call("dif_sliced_spmm_f32", "dif_sliced_spmm_f32", dev, _ptr(sl.entries), _ptr(sl.table), sl.run_plan, _ptr(ys),
                    _ptr(rowptr), _ptr(dinv), _ptr(sl.order), _ptr(sl.parts), n_pos, int(n_src), int(row_begin), int(n_rows),
                    int(F), _ptr(attn), lda, float(attn_scale), float(gcn_scale), _ptr(out), F, _ptr(ws), ws_bytes)
         return out

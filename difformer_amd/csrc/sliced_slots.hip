@@ -6,7 +6,7 @@
 // rows share a slot, and which slots share a wave, therefore decide the padding; the entry format and the sweep do not
 // care.  Four stages, all on the stream, no host read:
 //   a. block vectors b[row][tile] = (entries + 7) / 8 and the profile key (largest count descending, then the set of tiles
-//      that reach it: ops.packed_slot_order's key), sorted with the stable radix sort of the graph construction;
+//      that reach it: sliced.packed_slot_order's key), sorted with the stable radix sort of the graph construction;
 //   b. greedy slots: the sorted rows are cut into windows of 1,024 = 16 slots; one workgroup per window seeds a slot with
 //      the remaining row of the largest block total and adds, 63 times, the remaining row that raises the slot's
 //      per-tile maximum vector m least, sum_t max(0, b[row][t] - m[t]); ties: the larger total, then the lower row id;

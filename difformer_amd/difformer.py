@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from . import sliced
 from . import autograd_ops as ag
 from . import staging
 from . import tiny
@@ -506,7 +507,7 @@ class DIFFormer(nn.Module):
         if ag._needs_grad(x, fc.weight, fc.bias, bn.weight, bn.bias, *conv0._qkv_list()):
             return None
         csr = ops.csr_cache.get(edge_index, None, x.shape[0], hidden * 4)
-        sl = csr.sliced(0, x.shape[0], hidden) if x.shape[0] == csr.num_nodes else None
+        sl = sliced.rows_format(csr, x.dtype, x.shape[0], hidden)
         if sl is None:
             return None
         if self._single_copy(x, hidden, csr):                  # the hidden rows are left as the slice-major copy alone

@@ -17,6 +17,7 @@ import os
 
 import torch
 
+from . import sliced
 from .dist import RowShard
 from .tensor_cache import MISS, TensorCache, param_key, tensor_version      # (both functions are part of this module's surface)
 
@@ -147,141 +148,16 @@ def choose_shard_blocks(num_nodes, row_bytes, nnz, shard):
     return None
 
 
-SLICED_MIN_DEGREE = 48      # entries per row from which the LDS-staged product beats the gather kernels
-SLICED_MIN_ROWS = 8192
-
-
 def sliced_tiling(num_nodes, F, nnz, edge_weight, shard, elem_size):
     """(n_tiles, tile_rows) the feature-sliced product would use for this graph, or None when it is not a candidate
-    (edge weights, non-fp32 rows, sparse or small graph).  csr_cache builds the CSR with that blocking.  A row shard
-    has its own tiling (source splits: a multiple of 2, 4 or 8 tiles, include/difformer_hip.h)."""
-    if edge_weight is not None or elem_size != 4:
-        return None
-    if F % 4 or F > 256 or num_nodes < SLICED_MIN_ROWS or nnz < SLICED_MIN_DEGREE * num_nodes:
+    (sliced.candidate: edge weights, non-fp32 rows, sparse or small graph).  csr_cache builds the CSR with that blocking.
+    A row shard has its own tiling (source splits: a multiple of 2, 4 or 8 tiles, include/difformer_hip.h)."""
+    if not sliced.candidate(num_nodes, nnz, F, edge_weight is not None, elem_size):
         return None
     be = get_backend()
     n_rows = shard.n_local if (shard is not None and shard.world > 1) else num_nodes
     plan = be.sliced_plan(num_nodes, n_rows, F) if hasattr(be, "sliced_plan") else None
-    return None if plan is None else (int(plan[7]), int(plan[6]))
-
-
-SLICED_SPLIT_FACTOR = 4.0   # rows beyond this multiple of the mean degree are split into lock-step parts (Zipf C4: 2-6 within 4 %)
-SLICED_MAX_PARTS = 64       # one slot
-
-
-# Two schedules of the format (DESIGN.md section 3).  strict: natural row order, no two lanes of a hardware lane group on
-# one bank quad in a step.  packed (near-uniform degrees only): rows with equal per-tile block counts share a slot and a
-# quad may be read by two lanes of a step -- fewer padded steps for a few 2-way shared LDS reads, a longer cold build.
-# DIFFORMER_SLICED_SCHEDULE = strict | packed | auto (default); auto packs where the build is paid back within 64
-# launches (one short training run, or a few evaluations of a 4-layer model).  Measured on the MI355X at F = 64
-# (profiles/r07_experiments.md, profiles/r12_experiments.md): against the strict schedule a launch saves
-#    2.4 M entries: 1.4 us    10 M: 8 us    30 M: 15 us    79 M (headline): 35 us, 41 us with the dealt slot order
-# and the cold build of CSR + format, as `bench.py --full` times it on the headline graph, goes from 9.1 ms (strict) to
-# 10.0 ms (packed_slot_order) and 11.6 ms (the dealt order: 1.9 ms of device time for its two sorts, the greedy windows and
-# the deal).  2.45 ms / 64 = 38 us per launch: linear between the 30 M point (17 us with the dealt order's share) and the
-# 79 M point (41 us) that is ~73 M entries.
-SLICED_PACKED_MIN_ENTRIES = 72_000_000
-SLICED_PACKED_MAX_TILES = 40  # the slot order's key holds one bit per tile in an int64
-
-
-def sliced_schedule():
-    mode = os.environ.get("DIFFORMER_SLICED_SCHEDULE", "auto").strip().lower() or "auto"
-    if mode not in ("strict", "packed", "auto"):
-        raise ValueError(f"DIFFORMER_SLICED_SCHEDULE={mode!r}: expected strict, packed or auto")
-    return mode
-
-
-# Which rows share a slot of the packed schedule, and which slots share a wave (DESIGN.md section 3):
-# DIFFORMER_SLICED_SLOTS = dealt (default): greedy slots by tile profile, dealt to the waves against their running envelope,
-# all on the device (csrc/sliced_slots.hip); profile: packed_slot_order below, slots dealt in order -- also what a geometry
-# the device call does not cover gets.
-def sliced_slots():
-    mode = os.environ.get("DIFFORMER_SLICED_SLOTS", "dealt").strip().lower() or "dealt"
-    if mode not in ("profile", "dealt"):
-        raise ValueError(f"DIFFORMER_SLICED_SLOTS={mode!r}: expected profile or dealt")
-    return mode
-
-
-def packed_order(be, rowptr, blkptr, n_src, NT, row_begin, n_rows, plan):
-    """The row order of the packed schedule under DIFFORMER_SLICED_SLOTS: int32 [n_rows] on the device."""
-    order = None
-    if sliced_slots() == "dealt" and hasattr(be, "sliced_slot_order"):
-        order = be.sliced_slot_order(rowptr, blkptr, n_src, row_begin, n_rows, plan)
-    return packed_slot_order(rowptr, blkptr, n_src, NT, row_begin, n_rows) if order is None else order
-
-
-def packed_slot_order(rowptr, blkptr, n_src, NT, row_begin, n_rows):
-    """Rows of a near-uniform graph in the order that forms the slots of the packed schedule: by the largest per-tile
-    block count (8-step blocks, descending), then by the set of tiles that reach it, stable -- the 64 lock-step rows of
-    a slot then end their rounds in the same block in (nearly) every tile.  int32 [n_rows], on the device."""
-    if NT > 1:
-        cnt = blkptr.view(NT + 1, n_src)[:, row_begin: row_begin + n_rows]
-        blocks = (cnt[1:] - cnt[:-1] + 7) // 8
-    else:
-        blocks = ((rowptr[row_begin + 1: row_begin + n_rows + 1] - rowptr[row_begin: row_begin + n_rows] + 7) // 8)[None, :]
-    top = blocks.max(dim=0).values.to(torch.int64)
-    weights = torch.ones(NT, dtype=torch.int64, device=blocks.device) << torch.arange(NT, device=blocks.device)
-    hot = ((blocks == top[None, :]).to(torch.int64) * weights[:, None]).sum(dim=0)
-    key = (top.max() - top) * (1 << NT) + hot
-    return torch.argsort(key, stable=True).to(torch.int32)
-
-
-# DIFFORMER_SLICED_POSITIONS = 1 (default): the format carries one 8-byte record {row, deg^-1/2} per row position, written
-# by the cold build, and the product's epilogue reads it as one coalesced line per (wave, round) instead of gathering
-# rowptr and taking the divide and square root again in each of the 16 slice-workgroups of a panel (DESIGN.md section 3).
-# 0: no records, the gathering epilogue -- the same results bit for bit.
-def sliced_positions():
-    mode = os.environ.get("DIFFORMER_SLICED_POSITIONS", "1").strip() or "1"
-    if mode not in ("0", "1"):
-        raise ValueError(f"DIFFORMER_SLICED_POSITIONS={mode!r}: expected 0 or 1")
-    return mode == "1"
-
-
-class SlicedAdjacency:
-    """Entry blocks + table + geometry of the feature-sliced product (include/difformer_hip.h, dif_sliced_*).
-    order: rows by descending degree (skewed graphs) or by tile profile (packed schedule); parts / n_pos: hub rows split
-    into lock-step parts ("row positions" in the header) -- then order has n_pos entries (-1 = padding) and plan is the
-    geometry of n_pos positions; quad_cap: 1 = strict schedule, 2 = packed; positions: the allocation of `entries`
-    holds the position records in front of them (backend sliced_build) and run_plan, the plan the product is called
-    with, says so.  The slice-major source copy is written with the same plan (its tiling)."""
-
-    def __init__(self, plan, entries, table, order=None, parts=None, n_pos=None, quad_cap=1, positions=False):
-        self.plan, self.entries, self.table, self.order = plan, entries, table, order
-        self.parts, self.n_pos, self.quad_cap, self.positions = parts, n_pos, int(quad_cap), bool(positions)
-        self.run_plan = get_backend().sliced_run_plan(plan, True) if self.positions else plan
-
-
-def split_positions(deg_sorted, order, cap, max_parts=SLICED_MAX_PARTS):
-    """Row positions for rows sorted by descending degree `deg_sorted` (their ids in `order`): a row of degree d takes
-    P = min(ceil(d / cap), max_parts) consecutive positions of ONE 64-position slot.  Rows with the same P are packed
-    64 // P to a slot (every P-class starts on a fresh slot), the unsplit rows follow in order.
-    -> (order2 int32 [n_pos] with -1 = empty, parts uint16-as-int16 [n_pos] = p | P << 8, n_pos).  Device tensor ops;
-    one host sync for the sizes (cold path)."""
-    dev = deg_sorted.device
-    d = deg_sorted.to(torch.int64)
-    P = torch.clamp((d + cap - 1) // cap, 1, max_parts)
-    n_hub = int((P > 1).sum())                                   # a prefix: the degrees are sorted
-    n = d.numel()
-    Ph = P[:n_hub]
-    vals, counts = torch.unique_consecutive(Ph, return_counts=True)
-    per_slot = 64 // vals
-    class_slots = (counts + per_slot - 1) // per_slot
-    class_base = torch.cumsum(class_slots, 0) - class_slots      # first slot of every class
-    class_first = torch.cumsum(counts, 0) - counts               # first hub row of every class
-    cls = torch.repeat_interleave(torch.arange(vals.numel(), device=dev), counts)
-    k = torch.arange(n_hub, device=dev) - class_first[cls]
-    pos0 = (class_base[cls] + k // per_slot[cls]) * 64 + (k % per_slot[cls]) * Ph
-    hub_slots = int(class_slots.sum())
-    n_pos = hub_slots * 64 + (n - n_hub)
-    order2 = torch.full((n_pos,), -1, dtype=torch.int32, device=dev)
-    parts = torch.full((n_pos,), 0x0100, dtype=torch.int16, device=dev)
-    row_of_part = torch.repeat_interleave(torch.arange(n_hub, device=dev), Ph)
-    p_idx = torch.arange(row_of_part.numel(), device=dev) - (torch.cumsum(Ph, 0) - Ph)[row_of_part]
-    pos = pos0[row_of_part] + p_idx
-    order2[pos] = order[:n_hub][row_of_part].to(torch.int32)
-    parts[pos] = (p_idx + (Ph[row_of_part] << 8)).to(torch.int16)
-    order2[hub_slots * 64:] = order[n_hub:].to(torch.int32)
-    return order2, parts, n_pos
+    return None if plan is None else (plan.NT, plan.T)
 
 
 class GraphCSR:
@@ -334,52 +210,15 @@ class GraphCSR:
         return csr
 
     def sliced(self, row_begin, n_rows, F):
-        """The feature-sliced LDS format of rows [row_begin, row_begin + n_rows) for F fp32 feature columns
-        (csrc/gcn_sliced.hip), built on first use -- or None when this graph keeps the gather kernels: edge weights,
-        an adjoint CSR, a blocking that is not the format's tiling, or a (row, tile) group beyond the 16-bit counters.
-        With skewed degrees (max > 2x mean) the 64-row slots are formed in descending-degree order, so that the lock-step
-        lanes of a slot carry lists of similar length."""
+        """sliced.build of rows [row_begin, row_begin + n_rows) for F fp32 feature columns (a SlicedAdjacency, or None when
+        this graph keeps the gather kernels), built on first use and kept with the CSR."""
         key = (int(row_begin), int(n_rows), int(F))
         if key not in self._sliced:
             self._sliced[key] = self._build_sliced(*key)
         return self._sliced[key]
 
-    def _build_sliced(self, row_begin, n_rows, F):
-        if self.weighted or self.nnz == 0 or (self.transposed and self.dinv is None):
-            return None
-        be = get_backend()
-        if self.num_nodes < SLICED_MIN_ROWS or self.nnz < SLICED_MIN_DEGREE * self.num_nodes or not hasattr(be, "sliced_plan"):
-            return None
-        plan = be.sliced_plan(self.num_nodes, n_rows, F)
-        if plan is None:
-            return None
-        T, NT = int(plan[6]), int(plan[7])
-        if NT != self.n_blocks or (NT > 1 and T != self.block_rows):
-            return None
-        deg = self.rowptr[row_begin + 1: row_begin + n_rows + 1] - self.rowptr[row_begin: row_begin + n_rows]
-        max_deg, total = (int(v) for v in torch.stack([deg.max(), deg.sum()]).tolist())       # one sync, cold path
-        order = parts = n_pos = None
-        quad_cap = 1
-        mode = sliced_schedule()
-        if max_deg * n_rows > 2 * total:
-            order = be.row_order(self.rowptr, row_begin, n_rows)[0]
-            cap = max(int(SLICED_SPLIT_FACTOR * total / n_rows), 64)
-            if max_deg > cap:
-                # hub rows run as several lock-step lanes of one slot instead of one long lane
-                order, parts, n_pos = split_positions(deg[order.long()], order, cap)
-                plan = be.sliced_plan(self.num_nodes, n_pos, F)
-                if plan is None or int(plan[6]) != T or int(plan[7]) != NT:
-                    return None
-        elif NT <= SLICED_PACKED_MAX_TILES and (mode == "packed" or (mode == "auto" and total >= SLICED_PACKED_MIN_ENTRIES)):
-            order = packed_order(be, self.rowptr, self.blkptr, self.num_nodes, NT, row_begin, n_rows, plan)
-            quad_cap = 2
-        # the records hold deg^-1/2 of this CSR's row lengths: not for an adjoint CSR, whose products bring the forward dinv
-        positions = sliced_positions() and self.dinv is None
-        built = be.sliced_build(self.rowptr, self.blkptr, self.src, self.num_nodes, self.nnz, row_begin, n_rows, F, plan, order,
-                                parts, n_pos, quad_cap, positions)
-        if built is None:
-            return None
-        return SlicedAdjacency(plan, built[0], built[1], order, parts, n_pos, quad_cap, positions)
+    def _build_sliced(self, row_begin, n_rows, F):     # (uncached)
+        return sliced.build(get_backend(), self, row_begin, n_rows, F)
 
     def row_sums(self):
         """A_hat 1 (float32 [N]): what the bias of the value projection turns into under the aggregation,
@@ -513,7 +352,7 @@ class _CSRCache(TensorCache):
                         _SLICED_FALLBACK_WARNED = True
                         import warnings
                         warnings.warn("difformer_amd: this graph does not fit the feature-sliced product (see "
-                                      "GraphCSR._build_sliced); using the gather kernels on their own blocking")
+                                      "sliced.build); using the gather kernels on their own blocking")
                     csr = GraphCSR.build(edge_index, edge_weight, num_nodes, nb2, block_rows=br2)
                     csr._format_checked = True
                     csr.weight_scale = scale
@@ -522,7 +361,7 @@ class _CSRCache(TensorCache):
     UNIFORM_ALWAYS = False       # tests: run the check on graphs of any size
     UNIFORM_MIN_EDGES = 4096     # below this the CSR build is a handful of launches and the check would double its host cost
     # ... and it only buys something where the unweighted graph takes kernels the weighted one cannot: the feature-sliced
-    # product (SLICED_MIN_ROWS nodes, SLICED_MIN_DEGREE entries per row).  A 1,068-node snapshot with fresh tensors per forward
+    # product (sliced.candidate: SLICED_MIN_ROWS nodes, SLICED_MIN_DEGREE entries per row).  A 1,068-node snapshot with fresh tensors per forward
     # (spatial-temporal/main.py:96-105) would pay two reductions and a host read per snapshot for the same gather kernels.
 
     def _uniform_weight(self, edge_weight, n_edges, num_nodes=None):
@@ -531,7 +370,7 @@ class _CSRCache(TensorCache):
         Remembered per weight tensor (identity + version)."""
         if n_edges < self.UNIFORM_MIN_EDGES or edge_weight.numel() != n_edges or not edge_weight.is_floating_point():
             return None
-        if num_nodes is not None and (num_nodes < SLICED_MIN_ROWS or n_edges < SLICED_MIN_DEGREE * num_nodes) and not self.UNIFORM_ALWAYS:
+        if num_nodes is not None and not sliced.candidate(num_nodes, n_edges) and not self.UNIFORM_ALWAYS:
             return None
         if edge_weight.requires_grad and torch.is_grad_enabled():
             return None
@@ -651,7 +490,7 @@ def gcn_aggregate(csr: GraphCSR, x, attn=None, attn_scale=1.0, gcn_scale=1.0, sh
     be = get_backend()
     flat = lambda a: None if a is None else (a.materialize() if isinstance(a, LazyAttention) else a).reshape(n, H * D)
     if shard is None or shard.world <= 1:
-        sl = csr.sliced(0, n, H * D) if (x.dtype == torch.float32 and n == csr.num_nodes) else None
+        sl = sliced.rows_format(csr, x.dtype, n, H * D)
         out = _aggregate_rows(be, csr, sl, x.reshape(n, H * D), 0, n, flat(attn), attn_scale, gcn_scale, tail)
         return out.reshape(n, -1, D)           # [n, H, D]; [n, 1, D] after a tail
     # row-sharded: the one exchange step of this operator is the all-gather of the value rows (N*H*D elements)
@@ -664,7 +503,7 @@ def gcn_aggregate(csr: GraphCSR, x, attn=None, attn_scale=1.0, gcn_scale=1.0, sh
     F = H * D
     # dense unweighted graph: the shard's feature-sliced product (source tiles split over the workgroups of a panel) over
     # the gathered rows, as in the single-GPU branch above
-    sl = csr.sliced(row_begin, n_rows, F) if local.dtype == torch.float32 else None
+    sl = sliced.rows_format(csr, local.dtype, n_rows, F, shard)
     order = csr.row_order(row_begin, n_rows) if sl is None else None      # (built here, under the collective, on first use)
     rows = csr.block_rows
     split = (sl is None and csr.n_blocks > 1 and csr.nnz > 0 and F % 4 == 0 and F <= 256 and row_begin % rows == 0 and
@@ -943,9 +782,7 @@ def simple_layer_closed_form(x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_sca
     sharded = shard is not None and shard.world > 1
     if sharded and csr is not None and slice_sharded(shard, C, x.dtype):
         return _closed_form_slice_sharded(be, x, Wq, bq, Wk, bk, Wv, bv, csr, attn_scale, gcn_scale, *tail, shard, head)
-    sl = None
-    if csr is not None and (sharded or n == csr.num_nodes) and x.dtype == torch.float32:
-        sl = csr.sliced(shard.row_begin if sharded else 0, n, C)
+    sl = sliced.rows_format(csr, x.dtype, n, C, shard)
     handle = shard.all_gather_rows_async(x) if (sharded and csr is not None) else None
     have = carry.products if (carry is not None and not sharded) else None
     if have is not None and not (have["x"] is x and have["sl"] is sl):

@@ -9,7 +9,7 @@ EMPTY (order = -1, the padding mechanism of the hub-row split) -- an empty last 
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from difformer_amd import ops
+from difformer_amd import ops, sliced
 from bench import make_graph
 
 dev = torch.device("cuda:0")
@@ -65,7 +65,7 @@ def uneven(rounds):
     order, parts = order.to(dev), parts.to(dev)
     built = be.sliced_build(csr.rowptr, csr.blkptr, csr.src, n, csr.nnz, 0, n, C, plan, order, parts, G * 64)
     assert built is not None
-    return ops.SlicedAdjacency(plan, built[0], built[1], order, parts, G * 64)
+    return sliced.SlicedAdjacency(plan, built[0], built[1], order, parts, G * 64)
 
 
 lo, med, err = timed(base)

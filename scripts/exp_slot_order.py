@@ -12,7 +12,7 @@ Prints per variant: the block count the row envelopes alone predict, the block c
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import make_graph
-from difformer_amd import ops
+from difformer_amd import ops, sliced
 dev = torch.device("cuda:0")
 n, pairs, F = 132534, 39561252, 64
 if len(sys.argv) > 2:
@@ -26,7 +26,7 @@ slices, panels, G, PW, W, R, T, NT = (int(v) for v in plan)
 
 
 def slot_order():
-    return ops.packed_slot_order(csr.rowptr, csr.blkptr, n, NT, 0, n)
+    return sliced.packed_slot_order(csr.rowptr, csr.blkptr, n, NT, 0, n)
 
 
 def predicted(order):
@@ -57,7 +57,7 @@ if __name__ == "__main__":
             built = be.sliced_build(csr.rowptr, csr.blkptr, csr.src, n, csr.nnz, 0, n, F, plan, order, None, None, cap)
             torch.cuda.synchronize()
             build_ms = (time.perf_counter() - t0) * 1e3
-            sl = ops.SlicedAdjacency(plan, built[0], built[1], order, None, None, cap)
+            sl = sliced.SlicedAdjacency(plan, built[0], built[1], order, None, None, cap)
             nb = int(sl.table[-1])
             ys = be.sliced_prescale(x, csr.rowptr, n, sl.plan)
             for _ in range(5):

@@ -30,7 +30,7 @@ from conftest import rel_err
 from fake_backend import OracleBackend
 from guarded import GuardedArena, guarded_inputs, poisoned_allocations  # noqa: F401
 from oracle import difformer_oracle as orc
-from test_gpu_sliced_packed import schedule  # noqa: F401  (forces DIFFORMER_SLICED_SCHEDULE)
+from sliced_format import schedule  # noqa: F401  (forces DIFFORMER_SLICED_SCHEDULE)
 
 TOL, BF16_TOL = 1e-4, 1e-2
 F32, BF16 = torch.float32, torch.bfloat16

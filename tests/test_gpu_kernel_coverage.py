@@ -516,8 +516,8 @@ def test_layer_tail_backward_every_width(hidden, dev):
 
 
 # ================================================================== both sides of the host's dispatch thresholds
-# The host picks kernel families by thresholds fitted on synthetic graphs (ops.SLICED_MIN_DEGREE = 48 entries per row,
-# ops.SLICED_MIN_ROWS = 8,192 nodes, ops.MIX_THRESHOLD = 2.5, 16 entries per row for a wave per row): a graph just below and
+# The host picks kernel families by thresholds fitted on synthetic graphs (sliced.SLICED_MIN_DEGREE = 48 entries per row,
+# sliced.SLICED_MIN_ROWS = 8,192 nodes, ops.MIX_THRESHOLD = 2.5, 16 entries per row for a wave per row): a graph just below and
 # one just above each must give the oracle's numbers, and must take the families the threshold is meant to separate.
 def _regular_graph(n, per_row, seed):
     """exactly `per_row` entries in every row: per_row - 1 random sources + the self loop (main.py:75-76)."""

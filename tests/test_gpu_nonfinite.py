@@ -15,7 +15,7 @@ import torch
 from conftest import rel_err
 from guarded import poisoned_allocations  # noqa: F401  (the fixture)
 from oracle import difformer_oracle as orc
-from test_gpu_sliced_packed import schedule  # noqa: F401  (the fixture that forces DIFFORMER_SLICED_SCHEDULE)
+from sliced_format import schedule  # noqa: F401  (the fixture that forces DIFFORMER_SLICED_SCHEDULE)
 
 pytestmark = pytest.mark.gpu
 

@@ -17,55 +17,9 @@ import torch
 from conftest import rel_err
 from guarded import poisoned_allocations  # noqa: F401  (the fixture)
 from oracle import difformer_oracle as orc
+from sliced_format import check_format, dev, env, ragged_graph, records, skewed_graph  # noqa: F401  (dev, env: fixtures)
 
 D = 64
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture
-def env(monkeypatch):
-    """env(positions, schedule=None, slots=None): the three switches of the format (None = unset), on a cold CSR cache."""
-    from difformer_amd import ops
-
-    def set_(positions, schedule=None, slots=None):
-        for name, v in (("DIFFORMER_SLICED_POSITIONS", positions), ("DIFFORMER_SLICED_SCHEDULE", schedule),
-                        ("DIFFORMER_SLICED_SLOTS", slots)):
-            if v is None:
-                monkeypatch.delenv(name, raising=False)
-            else:
-                monkeypatch.setenv(name, str(v))
-        ops.csr_cache.clear()
-    yield set_
-    ops.csr_cache.clear()
-
-
-def _graph(n, lo, hi, seed, orphan=None):
-    """Every node receives lo..hi entries from random sources (repeats included) and its self loop; `orphan` receives
-    nothing at all (no self loop either), so its degree is 0."""
-    g = torch.Generator().manual_seed(seed)
-    deg = torch.randint(lo, hi + 1, (n,), generator=g)
-    if orphan is not None:
-        deg[orphan] = 0
-    dst = torch.repeat_interleave(torch.arange(n), deg)
-    src = torch.randint(0, n, (dst.numel(),), generator=g)
-    loops = torch.arange(n)
-    if orphan is not None:
-        loops = loops[loops != orphan]
-    return torch.stack([torch.cat([src, loops]), torch.cat([dst, loops])])
-
-
-def _skewed(n, seed, hubs=40):
-    """test_gpu_sliced_packed.py's skewed graph: half of the entries of a 64-per-row graph go to 40 hub rows."""
-    ei = _graph(n, 63, 63, seed)
-    g = torch.Generator().manual_seed(seed + 1)
-    half = ei.shape[1] // 2
-    ei[1, :half] = torch.randint(0, hubs, (half,), generator=g) * (n // hubs)
-    return ei
 
 
 _CASES = {}
@@ -74,30 +28,21 @@ _CASES = {}
 def _case(name):
     """(n, edge_index, x [n, 1, D], float64 oracle [n, D]) -- built once, shared, never modified."""
     if name not in _CASES:
-        n, ei = {"one_tile": lambda: (8205, _graph(8205, 47, 59, 1)),
-                 "four_tiles": lambda: (40000, _graph(40000, 59, 59, 2)),
-                 "skewed": lambda: (12000, _skewed(12000, 3)),
-                 "orphan": lambda: (8205, _graph(8205, 47, 59, 4, orphan=4321))}[name]()
+        n, ei = {"one_tile": lambda: (8205, ragged_graph(8205, 47, 59, 1)),
+                 "four_tiles": lambda: (40000, ragged_graph(40000, 59, 59, 2)),
+                 # half of the entries of a 64-per-row graph go to 40 hub rows
+                 "skewed": lambda: (12000, skewed_graph(12000, None, 3, base=ragged_graph(12000, 63, 63, 3))),
+                 "orphan": lambda: (8205, ragged_graph(8205, 47, 59, 4, orphan=4321))}[name]()
         x = torch.randn(n, 1, D, generator=torch.Generator().manual_seed(n))
         ref = orc.gcn_conv(x.double().numpy(), ei.numpy(), None)[:, 0, :]
         _CASES[name] = (n, ei, x, ref)
     return _CASES[name]
 
 
-def _records(sl):
-    """The records in front of sl.entries -> (row int32 [G * 64], scale float32 [G * 64])."""
-    G = int(sl.plan[2])
-    off = sl.entries.storage_offset()
-    assert off >= G * 256
-    raw = torch.empty(0, dtype=torch.int16, device=sl.entries.device).set_(sl.entries.untyped_storage(), off - G * 256, (G * 256,))
-    rec = raw.view(torch.int32).view(G * 64, 2)
-    return rec[:, 0].clone(), rec[:, 1].clone().view(torch.float32)
-
-
 def _check_records(sl, csr, lo, cnt):
     """Rows: order (or the natural order) padded with -1 to whole slots; scales: deg^-1/2 of the CSR's row lengths."""
     G = int(sl.plan[2])
-    row, scale = _records(sl)
+    row, scale = records(sl)
     want = torch.full((G * 64,), -1, dtype=torch.int32, device=row.device)
     n_pos = cnt if sl.n_pos is None else sl.n_pos
     want[:n_pos] = sl.order if sl.order is not None else torch.arange(cnt, dtype=torch.int32, device=row.device)
@@ -116,7 +61,7 @@ def _forward(name, dev, env, schedule=None, slots=None):
     eid, xd = ei.to(dev), x.to(dev)
     got = {}
     for positions in ("1", "0"):
-        env(positions, schedule, slots)
+        env(schedule, slots, positions)
         csr = ops.csr_cache.get(eid, None, n, D * 4)
         sl = csr.sliced(0, n, D)
         assert sl is not None and sl.positions == (positions == "1")
@@ -156,7 +101,7 @@ def test_skewed_graph_with_split_rows_and_empty_positions(dev, env):
 @pytest.mark.gpu
 def test_row_without_incoming_entries_is_zero(dev, env):
     out, sl, _ = _forward("orphan", dev, env)
-    row, scale = _records(sl)
+    row, scale = records(sl)
     assert float(scale[row == 4321]) == 0.0
     assert bool((out[4321] == 0).all()) and bool(torch.isfinite(out).all())
 
@@ -173,7 +118,7 @@ def test_both_ranks_of_a_two_way_row_shard(dev, env):
         lo, cnt = sh.row_begin, sh.n_local
         got = {}
         for positions in ("1", "0"):
-            env(positions, "packed", "dealt")
+            env("packed", "dealt", positions)
             be = ops.get_backend()
             csr = ops.csr_cache.get(eid, None, n, D * 4, sh)
             sl = csr.sliced(lo, cnt, D)
@@ -199,7 +144,7 @@ def test_a_product_with_its_own_dinv_keeps_the_gathering_epilogue(dev, env):
     dinv = (0.5 + torch.rand(n, generator=torch.Generator().manual_seed(10))).to(dev)
     grads, direct = {}, {}
     for positions in ("1", "0"):
-        env(positions)
+        env(positions=positions)
         xd = x.to(dev).requires_grad_(True)
         gcn_conv(xd, eid, None).backward(gout)
         grads[positions] = xd.grad.clone()
@@ -219,7 +164,7 @@ def test_a_product_with_its_own_dinv_keeps_the_gathering_epilogue(dev, env):
 @pytest.mark.gpu
 def test_two_calls_and_a_graph_replay_of_a_two_layer_forward_agree(dev, env):
     from difformer_amd import DIFFormer, GraphedForward, ops
-    env("1")
+    env(positions="1")
     torch.manual_seed(7)
     n, ei, _, _ = _case("one_tile")
     model = DIFFormer(24, D, 5, num_layers=2, kernel="simple").to(dev).eval()
@@ -246,33 +191,97 @@ def test_records_between_guard_bands(name, dev, env, poisoned_allocations):
     output, which is itself poisoned), and nothing is written outside the allocation."""
     out, sl, _ = _forward(name, dev, env)
     assert bool(torch.isfinite(out).all())
-    row, scale = _records(sl)
+    row, scale = records(sl)
     assert bool(torch.isfinite(scale).all())
     poisoned_allocations.check()
 
 
-def test_switch_rejects_unknown_values(monkeypatch):
+@pytest.mark.gpu
+@pytest.mark.parametrize("schedule", ["strict", "packed"])
+def test_the_format_checker_fails_on_a_corrupted_format(schedule, dev, env):
+    """check_format (tests/sliced_format.py) on host copies of the smallest format there is -- one tile, a partial last slot,
+    a partly empty last round: it passes on the copy as built and raises for each of five single corruptions.  Every
+    corruption keeps what the other rules look at (a cell that changes keeps its bank quad where the content is the point,
+    and its content where the bank rule is), so each rule is shown to fail on its own.  No kernel sees the corrupted data."""
+    from types import SimpleNamespace
+
     from difformer_amd import ops
+    from sliced_format import HW_GROUPS
+    n, ei, _, _ = _case("one_tile")
+    env(schedule)
+    csr = ops.csr_cache.get(ei.to(dev), None, n, D * 4)
+    sl = csr.sliced(0, n, D)
+    cap = 2 if schedule == "packed" else 1
+    assert list(sl.plan) == [16, 16, 129, 80, 5, 2, 8208, 1] and sl.quad_cap == cap and sl.parts is None
+    R, T = int(sl.plan[5]), int(sl.plan[6])
+    host_csr = SimpleNamespace(n_blocks=csr.n_blocks, rowptr=csr.rowptr.cpu(), src=csr.src.cpu(), blkptr=None)
+    entries, table = sl.entries.cpu().numpy(), sl.table.cpu().numpy()
+    order = None if sl.order is None else sl.order.cpu()
+
+    def check(e=entries, t=table):
+        copy = SimpleNamespace(plan=sl.plan, entries=torch.from_numpy(e), table=torch.from_numpy(t), order=order, parts=None,
+                               n_pos=None, quad_cap=cap)
+        return check_format(copy, ei, n, host_csr)
+
+    def cells(a):                                   # [block, lane, step] view of a flat entry array
+        return a.view(np.uint16).reshape(-1, 64, 8)[: int(table[-1])]
+    check()                                         # as built
+    ent0, grp = cells(entries), HW_GROUPS[0]
+    # (a) / (b): `cap` zero-row reads of a lane group move onto the quad of one more of its lanes -> cap + 1 lanes on it
+    b, s = np.argwhere((ent0[:, grp, :] >= T).sum(axis=1) >= cap)[0]
+    moved = [k for k in grp if ent0[b, k, s] >= T][:cap]
+    other = next(k for k in grp if k not in moved)
+    e = entries.copy()
+    cells(e)[b, moved, s] = T + (ent0[b, other, s] & 15)
+    with pytest.raises(AssertionError, match="more than two lanes" if cap == 2 else "bank conflict"):
+        check(e)
+
+    def alone(b, k, s):                             # no other lane of its lane group reads this cell's quad in this step
+        lanes = next(g for g in HW_GROUPS if k in g)
+        return int(((ent0[b, lanes, s] & 15) == (ent0[b, k, s] & 15)).sum()) == 1
+    # (c) one real entry becomes a zero-row read of the same quad
+    b, k, s = next(c for c in np.argwhere(ent0 < T) if alone(*c))
+    e = entries.copy()
+    cells(e)[b, k, s] = T + (ent0[b, k, s] & 15)
+    with pytest.raises(AssertionError):
+        check(e)
+    # (d) two lanes of a lane group exchange their entries of one step
+    k0, k1 = grp[:2]
+    b, s = next((b, s) for b, s in np.argwhere((ent0[:, [k0, k1], :] < T).all(axis=1)) if ent0[b, k0, s] != ent0[b, k1, s])
+    e = entries.copy()
+    cells(e)[b, [k0, k1], s] = ent0[b, [k1, k0], s]
+    with pytest.raises(AssertionError):
+        check(e)
+    # (e) a table row whose round lengths increase
+    t = table.copy()
+    rows = t[:-1].reshape(-1, R + 1)
+    i = int(np.argwhere(rows[:, 1] > rows[:, R])[0, 0])
+    rows[i, [1, R]] = rows[i, [R, 1]]
+    with pytest.raises(AssertionError, match="round lengths"):
+        check(t=t)
+
+
+def test_switch_rejects_unknown_values(monkeypatch):
+    from difformer_amd import sliced
     for v, want in (("1", True), ("0", False), ("", True), (" 1 ", True)):
         monkeypatch.setenv("DIFFORMER_SLICED_POSITIONS", v)
-        assert ops.sliced_positions() is want
+        assert sliced.sliced_positions() is want
     monkeypatch.delenv("DIFFORMER_SLICED_POSITIONS")
-    assert ops.sliced_positions() is True
+    assert sliced.sliced_positions() is True
     for v in ("2", "on", "true", "-1"):
         monkeypatch.setenv("DIFFORMER_SLICED_POSITIONS", v)
         with pytest.raises(ValueError):
-            ops.sliced_positions()
+            sliced.sliced_positions()
 
 
 def test_backend_sizes_the_record_section_from_the_plan():
-    import ctypes
-
-    from difformer_amd import backend_hip as bh
-    plan = (ctypes.c_int32 * 8)(16 | 1 << 16, 16, 2071, 240, 15, 9, 10208, 13)
-    assert bh.sliced_record_elems(plan) == 0                                   # no bit: no records
-    run = bh.sliced_run_plan(plan, True)
+    from difformer_amd.sliced import SlicedPlan
+    plan = SlicedPlan(16 | 1 << 16, 16, 2071, 240, 15, 9, 10208, 13)
+    assert plan.record_elems == 0                                              # no bit: no records
+    run = plan.with_records(True)
     assert list(plan) == [16 | 1 << 16, 16, 2071, 240, 15, 9, 10208, 13]       # the caller's plan stays as it is
     assert run[0] == 16 | 1 << 16 | 1 << 18 and list(run)[1:] == list(plan)[1:]
-    assert bh.sliced_record_elems(run) * 2 == 2071 * 64 * 8                    # 8 bytes per position of every slot, int16 elements
-    assert bh.sliced_record_elems(run) * 2 % 512 == 0                          # the blocks behind them keep their alignment
-    assert list(bh.sliced_run_plan(run, False)) == list(plan)
+    assert run.record_elems * 2 == 2071 * 64 * 8                               # 8 bytes per position of every slot, int16 elements
+    assert run.record_elems * 2 % 512 == 0                                     # the blocks behind them keep their alignment
+    assert list(run.with_records(False)) == list(plan)
+    assert (plan.slices, plan.panels, plan.G, plan.PW, plan.W, plan.R, plan.T, plan.NT) == (16, 16, 2071, 240, 15, 9, 10208, 13)

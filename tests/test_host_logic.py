@@ -395,10 +395,10 @@ def test_v2_training_backward_matches_reference_expression(fake_backend):
 
 
 def test_split_positions_layout():
-    """Row positions of the feature-sliced format when hub rows are split (ops.split_positions; "row positions" in
+    """Row positions of the feature-sliced format when hub rows are split (sliced.split_positions; "row positions" in
     include/difformer_hip.h): P = min(ceil(d / cap), 64) consecutive positions of one slot per row, part 0 first."""
     import numpy as np
-    from difformer_amd.ops import split_positions
+    from difformer_amd.sliced import split_positions
     g = torch.Generator().manual_seed(0)
     deg = torch.cat([torch.tensor([100000, 5000, 4999, 1300, 1201, 1200, 601, 601, 601]),
                      torch.randint(0, 600, (3000,), generator=g)])

@@ -10,12 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+from sliced_format import dense_graph, dev, env, headline_stats, product_vs_oracle, ragged_graph, slot_of  # noqa: F401  (dev, env: fixtures)
+
 WINDOW = 1024
 MAX_BLOCKS = 4095
-
-
-def slot_of(j, pw, PW):
-    return j * PW + ((PW - 1 - pw) if (j & 1) else pw)
 
 
 # ---- the restatement ------------------------------------------------------------------------------------------------
@@ -157,7 +155,7 @@ def test_restatement_places_every_row_once_and_repeats_itself(n, NT, PW, R):
 
 def test_restatement_pads_less_than_the_profile_order_on_poisson_rows():
     """Poisson (row, tile) counts at a scaled-down headline geometry: 13 tiles, 9 rounds.  The profile order dealt in order
-    is what ops.packed_slot_order gives; the dealt order must store clearly fewer blocks (the model of the headline graph:
+    is what sliced.packed_slot_order gives; the dealt order must store clearly fewer blocks (the model of the headline graph:
     1.247 -> 1.198 lane-steps per entry)."""
     rng = np.random.default_rng(0)
     n, NT, PW, R = 64 * 9 * 24, 13, 24, 9
@@ -170,54 +168,23 @@ def test_restatement_pads_less_than_the_profile_order_on_poisson_rows():
 
 
 def test_slots_switch_rejects_unknown_values(monkeypatch):
-    from difformer_amd import ops
+    from difformer_amd import sliced
     monkeypatch.setenv("DIFFORMER_SLICED_SLOTS", "best")
     with pytest.raises(ValueError):
-        ops.sliced_slots()
+        sliced.sliced_slots()
     monkeypatch.setenv("DIFFORMER_SLICED_SLOTS", "profile")
-    assert ops.sliced_slots() == "profile"
+    assert sliced.sliced_slots() == "profile"
     monkeypatch.delenv("DIFFORMER_SLICED_SLOTS")
-    assert ops.sliced_slots() == "dealt"
+    assert sliced.sliced_slots() == "dealt"
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture
-def env(monkeypatch):
-    def set_(schedule=None, slots=None):
-        from difformer_amd import ops
-        for name, value in (("DIFFORMER_SLICED_SCHEDULE", schedule), ("DIFFORMER_SLICED_SLOTS", slots)):
-            if value is None:
-                monkeypatch.delenv(name, raising=False)
-            else:
-                monkeypatch.setenv(name, value)
-        ops.csr_cache.clear()
-    yield set_
-    from difformer_amd import ops
-    ops.csr_cache.clear()
-
-
-def _ragged_graph(n, lo, hi, seed):
-    """lo..hi entries per destination row, uniform sources, plus self loops"""
-    g = torch.Generator().manual_seed(seed)
-    deg = torch.randint(lo, hi + 1, (n,), generator=g)
-    dst = torch.repeat_interleave(torch.arange(n), deg)
-    src = torch.randint(0, n, (int(deg.sum()),), generator=g)
-    return torch.cat([torch.stack([src, dst]), torch.arange(n).repeat(2, 1)], dim=1)
-
-
 def _graph(name):
-    from test_gpu_sliced_packed import _dense_graph
     if name == "one_tile":
-        return 8205, _ragged_graph(8205, 47, 59, seed=1)        # 48-60 entries with the self loop
+        return 8205, ragged_graph(8205, 47, 59, seed=1)        # 48-60 entries with the self loop
     if name == "four_tiles":
-        return 40000, _dense_graph(40000, 60, seed=7)
-    return 84000, _dense_graph(84000, 48, seed=84000 + 64)      # the graph of test_gpu_sliced_packed.py
+        return 40000, dense_graph(40000, 60, seed=7)
+    return 84000, dense_graph(84000, 48, seed=84000 + 64)      # the graph of test_gpu_sliced_packed.py
 
 
 def _device_order(be, csr, n, lo, cnt, F=64):
@@ -283,8 +250,7 @@ def test_device_order_equals_the_restatement(name, dev, env):
 @pytest.mark.gpu
 def test_built_format_under_dealt_against_profile_and_the_packed_guards(dev, env):
     """84,000 rows, 9 tiles.  The guards are those of test_gpu_sliced_packed.py's headline test."""
-    from difformer_amd import ops
-    from test_gpu_sliced_packed import _headline_stats
+    from difformer_amd import ops, sliced
     n, ei = _graph("nine_tiles")
     eid = ei.to(dev)
     blocks = {}
@@ -293,12 +259,12 @@ def test_built_format_under_dealt_against_profile_and_the_packed_guards(dev, env
         csr = ops.csr_cache.get(eid, None, n, 256)
         sl = csr.sliced(0, n, 64)
         assert sl is not None and sl.quad_cap == 2 and sl.order is not None
-        built, predicted, shared, minimum = _headline_stats(sl, csr, n, dev)
+        built, predicted, shared, minimum = headline_stats(sl, csr, n, dev)
         print(f"{slots}: built {built} blocks ({built * 512 / csr.nnz:.4f} lane-steps per entry), row envelope {predicted}, "
               f"shared cells {shared}, minimum {minimum}")
         blocks[slots] = built
         if slots == "profile":
-            assert torch.equal(sl.order, ops.packed_slot_order(csr.rowptr, csr.blkptr, n, int(sl.plan[7]), 0, n))
+            assert torch.equal(sl.order, sliced.packed_slot_order(csr.rowptr, csr.blkptr, n, int(sl.plan[7]), 0, n))
         else:
             assert built <= 1.05 * predicted
             assert shared <= 2 * minimum
@@ -309,14 +275,14 @@ def test_built_format_under_dealt_against_profile_and_the_packed_guards(dev, env
 def test_profile_reproduces_the_order_and_format_of_packed_slot_order(dev, env):
     """DIFFORMER_SLICED_SLOTS=profile is the format from before the device-side order, bit for bit: the same order, and the
     builder called with it directly gives the same entries and table."""
-    from difformer_amd import ops
+    from difformer_amd import ops, sliced
     env("packed", "profile")
     n, ei = _graph("four_tiles")
     csr = ops.csr_cache.get(ei.to(dev), None, n, 256)
     sl = csr.sliced(0, n, 64)
     be = ops.get_backend()
     plan = be.sliced_plan(n, n, 64)
-    order = ops.packed_slot_order(csr.rowptr, csr.blkptr, n, int(plan[7]), 0, n)
+    order = sliced.packed_slot_order(csr.rowptr, csr.blkptr, n, int(plan[7]), 0, n)
     entries, table = be.sliced_build(csr.rowptr, csr.blkptr, csr.src, n, csr.nnz, 0, n, 64, plan, order, None, None, 2)
     assert torch.equal(sl.order, order) and torch.equal(sl.entries, entries) and torch.equal(sl.table, table)
 
@@ -325,15 +291,14 @@ def test_profile_reproduces_the_order_and_format_of_packed_slot_order(dev, env):
 def test_products_under_dealt_vs_oracle_forward_adjoint_and_row_shard(dev, env):
     """The packed tests' product check (forward, adjoint, 2-way shard at 1e-5 of the float64 oracle; two products and two
     builds bit-identical) with the dealt order asked for by name, and the order really the device's."""
-    import test_gpu_sliced_packed as tp
-    from difformer_amd import ops
+    from difformer_amd import ops, sliced
     env("packed", "dealt")
-    tp.test_product_vs_oracle_forward_adjoint_and_row_shard("packed", dev, lambda mode: env(mode, "dealt"))
+    product_vs_oracle("packed", dev, lambda mode: env(mode, "dealt"))
     env("packed", "dealt")
     n, ei = _graph("four_tiles")
     csr = ops.csr_cache.get(ei.to(dev), None, n, 256)
     sl = csr.sliced(0, n, 64)
-    assert not torch.equal(sl.order, ops.packed_slot_order(csr.rowptr, csr.blkptr, n, int(sl.plan[7]), 0, n))
+    assert not torch.equal(sl.order, sliced.packed_slot_order(csr.rowptr, csr.blkptr, n, int(sl.plan[7]), 0, n))
     again = csr._build_sliced(0, n, 64)
     assert torch.equal(again.order, sl.order) and torch.equal(again.entries, sl.entries) and torch.equal(again.table, sl.table)
 
