@@ -1,5 +1,6 @@
-// Shared by the whole-model kernels for tiny graphs (tiny_model.hip: one workgroup; tiny_sigmoid_grid.hip: the `sigmoid`
-// kernel's O(n^2) pair loops spread over the chip): the argument block, the tape / scratch layouts and the per-row helpers.
+// Shared by the whole-model kernels for tiny graphs (tiny_model.hip: one workgroup; tiny_sigmoid_grid.hip / tiny_simple_grid.hip:
+// one launch per layer stage over the chip): the argument block, the tape / scratch layouts, the sum over nodes and the row
+// primitives.  The per-node stages built from them are in tiny_stages.h.
 #pragma once
 #include "dif_common.h"
 
@@ -222,7 +223,8 @@ __device__ __forceinline__ void matvec_t_add(const float* W, const float (&g)[DP
 
 __device__ __forceinline__ float sigmoidf(float v) { return 1.0f / (1.0f + expf(-v)); }
 
-// dropout of one row with the caller's uniforms: keep iff r >= p, scaled by 1 / (1 - p) (torch.nn.functional.dropout)
+// dropout of one row with the caller's uniforms: keep iff r >= p, scaled by 1 / (1 - p) (torch.nn.functional.dropout); the
+// backward applies the same mask and scale to the gradient
 template <int DP>
 __device__ __forceinline__ void dropout_row(float (&h)[DP], const float* rnd, int64_t at, int d, float p) {
     const float keep = 1.0f / (1.0f - p);

@@ -1,7 +1,8 @@
-// Shared by the grid plans of the whole-model kernels (tiny_sigmoid_grid.hip, tiny_simple_grid.hip): one launch per layer stage with
-// 64 nodes per workgroup; the backward's scratch layout and the per-node pieces that do not depend on the attention kernel.
+// Specific to the grid plans of the whole-model kernels (tiny_sigmoid_grid.hip, tiny_simple_grid.hip: one launch per layer stage,
+// 64 nodes per workgroup): the backward's scratch layout (GridScratch, the enums), the backward stages of tiny_stages.h bound to
+// that layout (tail_backward_common, input_backward; project for the forward), and grid_sums.  What a node computes is in tiny_stages.h.
 #pragma once
-#include "tiny_common.h"
+#include "tiny_stages.h"
 
 namespace tiny {
 
@@ -34,13 +35,7 @@ enum { kSG = 0, kQ = 1, kK = 2, kV = 3, kDA = 4 };
 template <int DP>
 __device__ __forceinline__ void project(const LayerW<DP>& w, bool use_weight, const float (&h)[DP], float (&q)[DP], float (&k)[DP],
                                         float (&v)[DP]) {
-    matvec<DP>(w.wq, w.bq, h, q);
-    matvec<DP>(w.wk, w.bk, h, k);
-    if (use_weight) matvec<DP>(w.wv, w.bv, h, v);
-    else {
-#pragma unroll
-        for (int m = 0; m < DP; ++m) v[m] = h[m];
-    }
+    TINY_PROJECT(w, use_weight, h, q, k, v)
 }
 
 // ======================================================================================================================
@@ -53,63 +48,9 @@ __device__ __forceinline__ void tail_backward_common(const TinyArgs& a, const Ta
                                                      float (&q)[DP], float (&k)[DP], float (&v)[DP]) {
     const int n = a.n, d = a.d;
     const size_t at_i = static_cast<size_t>(i) * DP;
-    float z[DP], dz[DP];
-    if (drop) {
-        const int64_t at = (static_cast<int64_t>(l + 1) * n + i) * d;
-#pragma unroll
-        for (int m = 0; m < DP; ++m)
-            if (m < d) dy[m] = (a.rnd[at + m] >= a.p_drop) ? dy[m] * keep : 0.f;
-    }
-    if (a.use_bn) {
-        load_row<DP>(tp.Z + (static_cast<size_t>(l + 1) * n + i) * DP, z);
-        float mean, rstd;
-        ln_stats<DP>(z, d, a.eps, mean, rstd);
-        float xh[DP], m1 = 0.f, m2 = 0.f;
-#pragma unroll
-        for (int m = 0; m < DP; ++m) {
-            xh[m] = (m < d) ? (z[m] - mean) * rstd : 0.f;
-            const float gw = w.lnw[m] * dy[m];
-            m1 += gw;
-            m2 += gw * xh[m];
-        }
-        m1 /= static_cast<float>(d);
-        m2 /= static_cast<float>(d);
-        float dyx[DP];
-#pragma unroll
-        for (int m = 0; m < DP; ++m) {
-            dyx[m] = dy[m] * xh[m];
-            dz[m] = (m < d) ? rstd * (w.lnw[m] * dy[m] - m1 - xh[m] * m2) : 0.f;
-        }
-        store_row<DP>(gs.per_layer(l, kDY) + at_i, dy);
-        store_row<DP>(gs.per_layer(l, kDYX) + at_i, dyx);
-    } else {
-#pragma unroll
-        for (int m = 0; m < DP; ++m) dz[m] = dy[m];
-    }
-    float dout[DP], dir[DP];
-#pragma unroll
-    for (int m = 0; m < DP; ++m) {
-        dout[m] = a.residual ? a.alpha * dz[m] : dz[m];
-        dir[m] = a.residual ? (1.0f - a.alpha) * dz[m] : 0.f;
-    }
-    store_row<DP>(gs.DIR + at_i, dir);
-    if (a.use_source) {
-        float acc[DP];
-        load_row<DP>(gs.DX0 + at_i, acc);
-#pragma unroll
-        for (int m = 0; m < DP; ++m) acc[m] += dout[m];
-        store_row<DP>(gs.DX0 + at_i, acc);
-    }
     const int set = l & 1;
-    if (a.use_graph) {
-        float sg[DP];
-#pragma unroll
-        for (int m = 0; m < DP; ++m) { sg[m] = a.g_s * dout[m]; datt[m] = a.a_s * dout[m]; }
-        store_row<DP>(gs.in_set(set, kSG) + at_i, sg);
-    } else {
-#pragma unroll
-        for (int m = 0; m < DP; ++m) datt[m] = dout[m];
-    }
+    TINY_TAIL_BACKWARD(w.lnw, tp.Z + (static_cast<size_t>(l + 1) * n + i) * DP, gs.per_layer(l, kDY) + at_i, gs.per_layer(l, kDYX) + at_i, gs.DIR + at_i,
+                       gs.DX0 + at_i, gs.in_set(set, kSG) + at_i, l, i, dy, datt)
     float h[DP];
     load_row<DP>(tp.H + (static_cast<size_t>(l) * n + i) * DP, h);
     project<DP>(w, a.use_weight, h, q, k, v);
@@ -126,54 +67,7 @@ __device__ __forceinline__ void input_backward(const TinyArgs& a, const Tape<DP>
     const int n = a.n, d = a.d;
     (void)n;
     const size_t at_i = static_cast<size_t>(i) * DP;
-    float z[DP];
-    if (a.use_source) {
-        float acc[DP];
-        load_row<DP>(gs.DX0 + at_i, acc);
-#pragma unroll
-        for (int m = 0; m < DP; ++m) dh[m] += acc[m];
-    }
-    if (drop) {
-        const int64_t at = static_cast<int64_t>(i) * d;
-#pragma unroll
-        for (int m = 0; m < DP; ++m)
-            if (m < d) dh[m] = (a.rnd[at + m] >= a.p_drop) ? dh[m] * keep : 0.f;
-    }
-    load_row<DP>(tp.Z + at_i, z);
-    float dpre[DP];
-    if (a.use_bn) {
-        float mean, rstd;
-        ln_stats<DP>(z, d, a.eps, mean, rstd);
-        float xh[DP], m1 = 0.f, m2 = 0.f, dyx[DP];
-#pragma unroll
-        for (int m = 0; m < DP; ++m) {
-            xh[m] = (m < d) ? (z[m] - mean) * rstd : 0.f;
-            const float yv = xh[m] * sLn0w[m] + sLn0b[m];
-            if (!(yv > 0.f)) dh[m] = 0.f;                                            // ReLU
-            const float gw = sLn0w[m] * dh[m];
-            m1 += gw;
-            m2 += gw * xh[m];
-            dyx[m] = dh[m] * xh[m];
-        }
-        m1 /= static_cast<float>(d);
-        m2 /= static_cast<float>(d);
-#pragma unroll
-        for (int m = 0; m < DP; ++m) dpre[m] = (m < d) ? rstd * (sLn0w[m] * dh[m] - m1 - xh[m] * m2) : 0.f;
-        store_row<DP>(gs.DY0 + at_i, dh);
-        store_row<DP>(gs.DYX0 + at_i, dyx);
-    } else {
-#pragma unroll
-        for (int m = 0; m < DP; ++m) dpre[m] = (m < d && z[m] > 0.f) ? dh[m] : 0.f;
-    }
-    store_row<DP>(gs.DPRE + at_i, dpre);
-    if (a.dx) {
-        for (int f = 0; f < a.f_in; ++f) {
-            float acc = 0.f;
-#pragma unroll
-            for (int m = 0; m < DP; ++m) acc += dpre[m] * sW0[m * kMaxIn + f];
-            a.dx[static_cast<size_t>(i) * a.f_in + f] = acc;
-        }
-    }
+    TINY_INPUT_BACKWARD(gs.DX0 + at_i, tp.Z + at_i, gs.DY0 + at_i, gs.DYX0 + at_i, gs.DPRE + at_i, i, dh)
 }
 
 // every sum over nodes of the backward (parameter gradients) from the per-layer operands: one workgroup per gradient

@@ -14,7 +14,13 @@
 // `outer_sum`: outputs x node-chunks spread over the threads, chunk partials in LDS, added in chunk order in float64 --
 // bitwise reproducible.  The sigmoid kernel's O(N^2) pair loop keeps the stationary node in registers and streams the
 // others through LDS tiles (uniform addresses: broadcast reads).
-#include "tiny_common.h"
+//
+// What ONE node computes in a stage (input layer, projections, closed-form `simple` row and its backward set-up, aggregation, layer
+// tail, output row, tail / LayerNorm / input-layer backward) is the TINY_* statement macros of tiny_stages.h, defined once for this
+// plan and the grid plans (tiny_sigmoid_grid.hip, tiny_simple_grid.hip); that file says why they are macros.  Here: the
+// one-workgroup plan's loops over nodes, its pair sweeps, its sums over nodes and 14 scratch slots, the graph preparation and
+// the C entry points.
+#include "tiny_stages.h"
 
 using namespace tiny;
 
@@ -37,44 +43,14 @@ __global__ __launch_bounds__(512) void tiny_forward_kernel(const TinyArgs a) {
     Tape<DP> tp(a.tape, n, L);
     const bool drop = a.training && a.rnd != nullptr && a.p_drop > 0.f;
 
-    for (int k = t; k < DP * kMaxIn; k += T) {
-        const int m = k / kMaxIn, f = k % kMaxIn;
-        sW0[k] = (m < d && f < a.f_in) ? a.w0[m * a.f_in + f] : 0.f;
-    }
-    for (int k = t; k < DP; k += T) {
-        sB0[k] = k < d ? a.b0[k] : 0.f;
-        sLn0w[k] = (k < d && a.use_bn) ? a.ln0w[k] : 0.f;
-        sLn0b[k] = (k < d && a.use_bn) ? a.ln0b[k] : 0.f;
-    }
-    for (int k = t; k < kMaxOut * DP; k += T) {
-        const int c = k / DP, m = k % DP;
-        sWo[k] = (c < a.c && m < d) ? a.wo[c * d + m] : 0.f;
-    }
-    for (int k = t; k < kMaxOut; k += T) sBo[k] = k < a.c ? a.bo[k] : 0.f;
+    TINY_LOAD_INPUT_CONSTS(sB0[k_] = k_ < d ? a.b0[k_] : 0.f;)
+    TINY_LOAD_OUTPUT_CONSTS(for (int k_ = t; k_ < kMaxOut; k_ += T) sBo[k_] = k_ < a.c ? a.bo[k_] : 0.f;)
     __syncthreads();
 
     // ---- input layer: Linear -> LayerNorm -> ReLU -> dropout (:188-192) ----
     for (int i = t; i < n; i += T) {
         float h[DP];
-#pragma unroll
-        for (int m = 0; m < DP; ++m) h[m] = sB0[m];
-        const float* xr = a.x + i * a.ldx;
-        for (int f = 0; f < a.f_in; ++f) {
-            const float xv = xr[f];
-#pragma unroll
-            for (int m = 0; m < DP; ++m) h[m] += sW0[m * kMaxIn + f] * xv;
-        }
-        store_row<DP>(tp.Z + static_cast<size_t>(i) * DP, h);
-        if (a.use_bn) {
-            float mean, rstd;
-            ln_stats<DP>(h, d, a.eps, mean, rstd);
-#pragma unroll
-            for (int m = 0; m < DP; ++m) h[m] = (m < d) ? (h[m] - mean) * rstd * sLn0w[m] + sLn0b[m] : 0.f;
-        }
-#pragma unroll
-        for (int m = 0; m < DP; ++m) h[m] = fmaxf(h[m], 0.f);
-        if (drop) dropout_row<DP>(h, a.rnd, static_cast<int64_t>(i) * d, d, a.p_drop);
-        store_row<DP>(tp.H + static_cast<size_t>(i) * DP, h);
+        TINY_INPUT_FORWARD(i, h)
     }
 
     for (int l = 0; l < L; ++l) {
@@ -86,13 +62,7 @@ __global__ __launch_bounds__(512) void tiny_forward_kernel(const TinyArgs a) {
         for (int i = t; i < n; i += T) {
             float h[DP], q[DP], k[DP], v[DP];
             load_row<DP>(Hl + static_cast<size_t>(i) * DP, h);
-            matvec<DP>(sL.wq, sL.bq, h, q);
-            matvec<DP>(sL.wk, sL.bk, h, k);
-            if (a.use_weight) matvec<DP>(sL.wv, sL.bv, h, v);
-            else {
-#pragma unroll
-                for (int m = 0; m < DP; ++m) v[m] = h[m];
-            }
+            TINY_PROJECT(sL, a.use_weight, h, q, k, v)
             store_row<DP>(tp.Q + static_cast<size_t>(i) * DP, q);
             store_row<DP>(tp.K + static_cast<size_t>(i) * DP, k);
             store_row<DP>(tp.V + static_cast<size_t>(i) * DP, v);
@@ -190,62 +160,11 @@ __global__ __launch_bounds__(512) void tiny_forward_kernel(const TinyArgs a) {
                     tp.DEN[static_cast<size_t>(l) * n + i] = static_cast<float>(den);
                 }
             } else if (live) {
-                const float q2 = sSum[DP * DP + 2 * DP], k2 = sSum[DP * DP + 2 * DP + 1];
-                const float s = 1.0f / (sqrtf(q2) * sqrtf(k2));                      // :20-21 global Frobenius norms
-                float den = 0.f;
-#pragma unroll
-                for (int m = 0; m < DP; ++m) den += q[m] * sSum[DP * DP + m];
-                den = s * den + static_cast<float>(n);                               // :31-38  (+N from qs.shape[0])
-#pragma unroll
-                for (int dd = 0; dd < DP; ++dd) {
-                    float num = 0.f;
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) num += q[m] * sSum[m * DP + dd];
-                    att[dd] = (s * num + sSum[DP * DP + DP + dd]) / den;             // :25-29
-                }
+                TINY_SIMPLE_ATTENTION_ROW(q, att)
             }
             if (live) {
-                store_row<DP>(tp.ATT + (static_cast<size_t>(l) * n + i) * DP, att);
                 float out[DP];
-                if (a.use_graph) {
-                    float g[DP];
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) g[m] = 0.f;
-                    const int e1 = a.rowptr[i + 1];
-                    for (int e = a.rowptr[i]; e < e1; ++e) {                          // :75-78, entries in edge order
-                        const float w = a.val[e];
-                        float vr[DP];
-                        load_row<DP>(tp.V + static_cast<size_t>(a.nbr[e]) * DP, vr);
-#pragma unroll
-                        for (int m = 0; m < DP; ++m) g[m] += w * vr[m];
-                    }
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) out[m] = a.a_s * att[m] + a.g_s * g[m]; // :130-134
-                } else {
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) out[m] = att[m];
-                }
-                float h[DP];
-                load_row<DP>(Hl + static_cast<size_t>(i) * DP, h);
-                if (a.use_source) {                                                  // :139-140
-                    float x0[DP];
-                    load_row<DP>(tp.H + static_cast<size_t>(i) * DP, x0);
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) out[m] += x0[m];
-                }
-                if (a.residual) {                                                    // :200-201
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) out[m] = a.alpha * out[m] + (1.0f - a.alpha) * h[m];
-                }
-                store_row<DP>(tp.Z + (static_cast<size_t>(l + 1) * n + i) * DP, out);
-                if (a.use_bn) {                                                      // :202-203
-                    float mean, rstd;
-                    ln_stats<DP>(out, d, a.eps, mean, rstd);
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) out[m] = (m < d) ? (out[m] - mean) * rstd * sL.lnw[m] + sL.lnb[m] : 0.f;
-                }
-                if (drop) dropout_row<DP>(out, a.rnd, (static_cast<int64_t>(l + 1) * n + i) * d, d, a.p_drop);   // :204
-                store_row<DP>(tp.H + (static_cast<size_t>(l + 1) * n + i) * DP, out);
+                TINY_LAYER_TAIL_FORWARD(tp.V, Hl + static_cast<size_t>(i) * DP, sL, l, i, att, out)
             }
         }
     }
@@ -253,12 +172,7 @@ __global__ __launch_bounds__(512) void tiny_forward_kernel(const TinyArgs a) {
     for (int i = t; i < n; i += T) {
         float h[DP];
         load_row<DP>(tp.H + (static_cast<size_t>(L) * n + i) * DP, h);
-        for (int c = 0; c < a.c; ++c) {
-            float acc = sBo[c];
-#pragma unroll
-            for (int m = 0; m < DP; ++m) acc += sWo[c * DP + m] * h[m];
-            a.y[static_cast<size_t>(i) * a.c + c] = acc;
-        }
+        TINY_OUTPUT_ROW(i, h)
     }
 }
 
@@ -291,18 +205,8 @@ __global__ __launch_bounds__(512) void tiny_backward_kernel(const TinyArgs a) {
     const bool drop = a.training && a.rnd != nullptr && a.p_drop > 0.f;
     const float keep = drop ? 1.0f / (1.0f - a.p_drop) : 1.0f;
 
-    for (int k = t; k < DP * kMaxIn; k += T) {
-        const int m = k / kMaxIn, f = k % kMaxIn;
-        sW0[k] = (m < d && f < a.f_in) ? a.w0[m * a.f_in + f] : 0.f;
-    }
-    for (int k = t; k < DP; k += T) {
-        sLn0w[k] = (k < d && a.use_bn) ? a.ln0w[k] : 0.f;
-        sLn0b[k] = (k < d && a.use_bn) ? a.ln0b[k] : 0.f;
-    }
-    for (int k = t; k < kMaxOut * DP; k += T) {
-        const int c = k / DP, m = k % DP;
-        sWo[k] = (c < a.c && m < d) ? a.wo[c * d + m] : 0.f;
-    }
+    TINY_LOAD_INPUT_CONSTS()
+    TINY_LOAD_OUTPUT_CONSTS()
     __syncthreads();
 
     // ---- output Linear: d H[L] = gy Wo; d Wo = gy^T H[L]; d bo = sum gy ----
@@ -310,11 +214,7 @@ __global__ __launch_bounds__(512) void tiny_backward_kernel(const TinyArgs a) {
         float g[DP];
 #pragma unroll
         for (int m = 0; m < DP; ++m) g[m] = 0.f;
-        for (int c = 0; c < a.c; ++c) {
-            const float gv = a.gy[static_cast<size_t>(i) * a.c + c];
-#pragma unroll
-            for (int m = 0; m < DP; ++m) g[m] += gv * sWo[c * DP + m];
-        }
+        TINY_OUTPUT_BACKWARD_ROW(i, g)
         store_row<DP>(DH + static_cast<size_t>(i) * DP, g);
         if (a.use_source) {
 #pragma unroll
@@ -345,73 +245,13 @@ __global__ __launch_bounds__(512) void tiny_backward_kernel(const TinyArgs a) {
         const float s = a.sigmoid ? 0.f : 1.0f / (sqrtf(q2) * sqrtf(k2));
         // ---- phase 1: tail backward, attention set-up, per node ----
         for (int i = t; i < n; i += T) {
-            float dy[DP], z[DP], dz[DP];
+            float dy[DP], datt[DP];
             load_row<DP>(DH + static_cast<size_t>(i) * DP, dy);
-            if (drop) {
-                const int64_t at = (static_cast<int64_t>(l + 1) * n + i) * d;
-#pragma unroll
-                for (int m = 0; m < DP; ++m)
-                    if (m < d) dy[m] = (a.rnd[at + m] >= a.p_drop) ? dy[m] * keep : 0.f;
-            }
-            if (a.use_bn) {
-                load_row<DP>(tp.Z + (static_cast<size_t>(l + 1) * n + i) * DP, z);
-                float mean, rstd;
-                ln_stats<DP>(z, d, a.eps, mean, rstd);
-                float xh[DP], m1 = 0.f, m2 = 0.f;
-#pragma unroll
-                for (int m = 0; m < DP; ++m) {
-                    xh[m] = (m < d) ? (z[m] - mean) * rstd : 0.f;
-                    const float gw = sL.lnw[m] * dy[m];
-                    m1 += gw;
-                    m2 += gw * xh[m];
-                }
-                m1 /= static_cast<float>(d);
-                m2 /= static_cast<float>(d);
-                float dyx[DP];
-#pragma unroll
-                for (int m = 0; m < DP; ++m) {
-                    dyx[m] = dy[m] * xh[m];
-                    dz[m] = (m < d) ? rstd * (sL.lnw[m] * dy[m] - m1 - xh[m] * m2) : 0.f;
-                }
-                store_row<DP>(DY + static_cast<size_t>(i) * DP, dy);
-                store_row<DP>(DYX + static_cast<size_t>(i) * DP, dyx);
-            } else {
-#pragma unroll
-                for (int m = 0; m < DP; ++m) dz[m] = dy[m];
-            }
-            float dout[DP], dir[DP];
-#pragma unroll
-            for (int m = 0; m < DP; ++m) {
-                dout[m] = a.residual ? a.alpha * dz[m] : dz[m];
-                dir[m] = a.residual ? (1.0f - a.alpha) * dz[m] : 0.f;
-            }
-            store_row<DP>(DIR + static_cast<size_t>(i) * DP, dir);
-            if (a.use_source) {
-                float acc[DP];
-                load_row<DP>(DX0 + static_cast<size_t>(i) * DP, acc);
-#pragma unroll
-                for (int m = 0; m < DP; ++m) acc[m] += dout[m];
-                store_row<DP>(DX0 + static_cast<size_t>(i) * DP, acc);
-            }
-            float datt[DP];
-            if (a.use_graph) {
-                float sg[DP];
-#pragma unroll
-                for (int m = 0; m < DP; ++m) { sg[m] = a.g_s * dout[m]; datt[m] = a.a_s * dout[m]; }
-                store_row<DP>(SG + static_cast<size_t>(i) * DP, sg);
-            } else {
-#pragma unroll
-                for (int m = 0; m < DP; ++m) datt[m] = dout[m];
-            }
+            TINY_TAIL_BACKWARD(sL.lnw, tp.Z + (static_cast<size_t>(l + 1) * n + i) * DP, DY + static_cast<size_t>(i) * DP, DYX + static_cast<size_t>(i) * DP,
+                               DIR + static_cast<size_t>(i) * DP, DX0 + static_cast<size_t>(i) * DP, SG + static_cast<size_t>(i) * DP, l, i, dy, datt)
             float h[DP], q[DP], k[DP], v[DP];
             load_row<DP>(Hl + static_cast<size_t>(i) * DP, h);
-            matvec<DP>(sL.wq, sL.bq, h, q);
-            matvec<DP>(sL.wk, sL.bk, h, k);
-            if (a.use_weight) matvec<DP>(sL.wv, sL.bv, h, v);
-            else {
-#pragma unroll
-                for (int m = 0; m < DP; ++m) v[m] = h[m];
-            }
+            TINY_PROJECT(sL, a.use_weight, h, q, k, v)
             store_row<DP>(Q + static_cast<size_t>(i) * DP, q);
             store_row<DP>(K + static_cast<size_t>(i) * DP, k);
             store_row<DP>(V + static_cast<size_t>(i) * DP, v);
@@ -425,34 +265,8 @@ __global__ __launch_bounds__(512) void tiny_backward_kernel(const TinyArgs a) {
                 store_row<DP>(DNUM + static_cast<size_t>(i) * DP, da);          // DA_i = d att_i / den_i
                 DDEN[i] = dl * rden;                                             // DL_i = (d att_i . att_i) / den_i
             } else {
-                float A[DP], b = 0.f;
-#pragma unroll
-                for (int dd = 0; dd < DP; ++dd) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) acc += q[m] * sSum[m * DP + dd];
-                    A[dd] = acc;
-                }
-#pragma unroll
-                for (int m = 0; m < DP; ++m) b += q[m] * sSum[DP * DP + m];
-                const float den = s * b + static_cast<float>(n);
-                float dnum[DP], dden = 0.f, ts = 0.f;
-#pragma unroll
-                for (int dd = 0; dd < DP; ++dd) {
-                    const float att = (s * A[dd] + sSum[DP * DP + DP + dd]) / den;
-                    dnum[dd] = datt[dd] / den;
-                    dden -= dnum[dd] * att;
-                    ts += dnum[dd] * A[dd];
-                }
-                ts += dden * b;
-                float dq[DP];
-#pragma unroll
-                for (int m = 0; m < DP; ++m) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int dd = 0; dd < DP; ++dd) acc += sSum[m * DP + dd] * dnum[dd];
-                    dq[m] = s * (acc + dden * sSum[DP * DP + m]);
-                }
+                float dnum[DP], dden = 0.f, ts = 0.f, dq[DP];
+                TINY_SIMPLE_BACKWARD_SETUP(q, datt, s, dnum, dden, ts, dq)
                 store_row<DP>(DNUM + static_cast<size_t>(i) * DP, dnum);
                 store_row<DP>(DQ + static_cast<size_t>(i) * DP, dq);
                 DDEN[i] = dden;
@@ -577,16 +391,7 @@ __global__ __launch_bounds__(512) void tiny_backward_kernel(const TinyArgs a) {
                 }
             }
             if (live) {
-                if (a.use_graph) {                      // adjoint of the aggregation: entries of the TRANSPOSED CSR, edge order
-                    const int e1 = a.rowptr[i + 1];
-                    for (int e = a.rowptr[i]; e < e1; ++e) {
-                        const float w = a.val[e];
-                        float gr[DP];
-                        load_row<DP>(SG + static_cast<size_t>(a.nbr[e]) * DP, gr);
-#pragma unroll
-                        for (int m = 0; m < DP; ++m) dv[m] += w * gr[m];
-                    }
-                }
+                if (a.use_graph) TINY_GATHER_ROWS(SG, i, dv)      // adjoint of the aggregation: the TRANSPOSED CSR, edge order
                 // padded columns carry nothing
 #pragma unroll
                 for (int m = 0; m < DP; ++m)
@@ -595,14 +400,7 @@ __global__ __launch_bounds__(512) void tiny_backward_kernel(const TinyArgs a) {
                 store_row<DP>(DK + static_cast<size_t>(i) * DP, dk);
                 store_row<DP>(DV + static_cast<size_t>(i) * DP, dv);
                 float dh[DP];
-                load_row<DP>(DIR + static_cast<size_t>(i) * DP, dh);
-                matvec_t_add<DP>(sL.wq, dq, dh);
-                matvec_t_add<DP>(sL.wk, dk, dh);
-                if (a.use_weight) matvec_t_add<DP>(sL.wv, dv, dh);
-                else {
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) dh[m] += dv[m];
-                }
+                TINY_BACK_PROJECT(DIR + static_cast<size_t>(i) * DP, sL, dq, dk, dv, dh)
                 store_row<DP>(DH + static_cast<size_t>(i) * DP, dh);
             }
         }
@@ -623,55 +421,10 @@ __global__ __launch_bounds__(512) void tiny_backward_kernel(const TinyArgs a) {
 
     // ---- input layer backward (:188-192) ----
     for (int i = t; i < n; i += T) {
-        float dy[DP], z[DP];
+        float dy[DP];
         load_row<DP>(DH + static_cast<size_t>(i) * DP, dy);
-        if (a.use_source) {
-            float acc[DP];
-            load_row<DP>(DX0 + static_cast<size_t>(i) * DP, acc);
-#pragma unroll
-            for (int m = 0; m < DP; ++m) dy[m] += acc[m];
-        }
-        if (drop) {
-            const int64_t at = static_cast<int64_t>(i) * d;
-#pragma unroll
-            for (int m = 0; m < DP; ++m)
-                if (m < d) dy[m] = (a.rnd[at + m] >= a.p_drop) ? dy[m] * keep : 0.f;
-        }
-        load_row<DP>(tp.Z + static_cast<size_t>(i) * DP, z);
-        float dpre[DP];
-        if (a.use_bn) {
-            float mean, rstd;
-            ln_stats<DP>(z, d, a.eps, mean, rstd);
-            float xh[DP], m1 = 0.f, m2 = 0.f, dyx[DP];
-#pragma unroll
-            for (int m = 0; m < DP; ++m) {
-                xh[m] = (m < d) ? (z[m] - mean) * rstd : 0.f;
-                const float yv = xh[m] * sLn0w[m] + sLn0b[m];
-                if (!(yv > 0.f)) dy[m] = 0.f;                                        // ReLU
-                const float gw = sLn0w[m] * dy[m];
-                m1 += gw;
-                m2 += gw * xh[m];
-                dyx[m] = dy[m] * xh[m];
-            }
-            m1 /= static_cast<float>(d);
-            m2 /= static_cast<float>(d);
-#pragma unroll
-            for (int m = 0; m < DP; ++m) dpre[m] = (m < d) ? rstd * (sLn0w[m] * dy[m] - m1 - xh[m] * m2) : 0.f;
-            store_row<DP>(DY + static_cast<size_t>(i) * DP, dy);
-            store_row<DP>(DYX + static_cast<size_t>(i) * DP, dyx);
-        } else {
-#pragma unroll
-            for (int m = 0; m < DP; ++m) dpre[m] = (m < d && z[m] > 0.f) ? dy[m] : 0.f;
-        }
-        store_row<DP>(DPRE + static_cast<size_t>(i) * DP, dpre);
-        if (a.dx) {
-            for (int f = 0; f < a.f_in; ++f) {
-                float acc = 0.f;
-#pragma unroll
-                for (int m = 0; m < DP; ++m) acc += dpre[m] * sW0[m * kMaxIn + f];
-                a.dx[static_cast<size_t>(i) * a.f_in + f] = acc;
-            }
-        }
+        TINY_INPUT_BACKWARD(DX0 + static_cast<size_t>(i) * DP, tp.Z + static_cast<size_t>(i) * DP, DY + static_cast<size_t>(i) * DP, DYX + static_cast<size_t>(i) * DP,
+                            DPRE + static_cast<size_t>(i) * DP, i, dy)
     }
     __syncthreads();
     if (a.use_bn) {

@@ -18,6 +18,10 @@
 // that is done with layer l writes layer l +- 1's rows while others still read layer l's.  Partial sums: every product rounded once
 // in float32, added in float64; the waves' chunks in a fixed order -- bitwise reproducible, as the one-workgroup kernels are.
 // Same tape, same scratch buffer, same C entry points (dif_tiny_forward_f32 / dif_tiny_backward_f32 pick the plan).
+//
+// The per-node work around the pair loops is the TINY_* stages of tiny_stages.h (one definition for the three plans) and, for the
+// backward, tail_backward_common / input_backward of tiny_grid.h, which run those stages on the grid plans' scratch layout.  Here:
+// the pair sweeps with fast_sigmoid, the key splits, the launch sequences and grid_sums_kernel.
 #include "tiny_grid.h"
 
 using namespace tiny;
@@ -73,39 +77,13 @@ __global__ __launch_bounds__(kWaves * 64) void grid_sigmoid_forward_kernel(const
     const bool drop = a.training && a.rnd != nullptr && a.p_drop > 0.f;
 
     if (stage == 0) {
-        for (int k = t; k < DP * kMaxIn; k += T) {
-            const int m = k / kMaxIn, f = k % kMaxIn;
-            sW0[k] = (m < d && f < a.f_in) ? a.w0[m * a.f_in + f] : 0.f;
-        }
-        for (int k = t; k < DP; k += T) {
-            sB0[k] = k < d ? a.b0[k] : 0.f;
-            sLn0w[k] = (k < d && a.use_bn) ? a.ln0w[k] : 0.f;
-            sLn0b[k] = (k < d && a.use_bn) ? a.ln0b[k] : 0.f;
-        }
+        TINY_LOAD_INPUT_CONSTS(sB0[k_] = k_ < d ? a.b0[k_] : 0.f;)
         load_layer<DP>(sNext, a.lp[0], d, a.use_weight, a.use_bn);
         __syncthreads();
         if (!live || t >= 64) return;
         // input layer: Linear -> LayerNorm -> ReLU -> dropout (:188-192)
         float h[DP];
-#pragma unroll
-        for (int m = 0; m < DP; ++m) h[m] = sB0[m];
-        const float* xr = a.x + i * a.ldx;
-        for (int f = 0; f < a.f_in; ++f) {
-            const float xv = xr[f];
-#pragma unroll
-            for (int m = 0; m < DP; ++m) h[m] += sW0[m * kMaxIn + f] * xv;
-        }
-        store_row<DP>(tp.Z + static_cast<size_t>(i) * DP, h);
-        if (a.use_bn) {
-            float mean, rstd;
-            ln_stats<DP>(h, d, a.eps, mean, rstd);
-#pragma unroll
-            for (int m = 0; m < DP; ++m) h[m] = (m < d) ? (h[m] - mean) * rstd * sLn0w[m] + sLn0b[m] : 0.f;
-        }
-#pragma unroll
-        for (int m = 0; m < DP; ++m) h[m] = fmaxf(h[m], 0.f);
-        if (drop) dropout_row<DP>(h, a.rnd, static_cast<int64_t>(i) * d, d, a.p_drop);
-        store_row<DP>(tp.H + static_cast<size_t>(i) * DP, h);
+        TINY_INPUT_FORWARD(i, h)
         float q[DP], k[DP], v[DP];
         project<DP>(sNext, a.use_weight, h, q, k, v);
         float* set = tp.qkv(0);
@@ -121,11 +99,7 @@ __global__ __launch_bounds__(kWaves * 64) void grid_sigmoid_forward_kernel(const
         load_layer<DP>(sL, a.lp[l], d, a.use_weight, a.use_bn);
         if (!last) load_layer<DP>(sNext, a.lp[l + 1], d, a.use_weight, a.use_bn);
         else {
-            for (int k = t; k < kMaxOut * DP; k += T) {
-                const int c = k / DP, m = k % DP;
-                sWo[k] = (c < a.c && m < d) ? a.wo[c * d + m] : 0.f;
-            }
-            for (int k = t; k < kMaxOut; k += T) sBo[k] = k < a.c ? a.bo[k] : 0.f;
+            TINY_LOAD_OUTPUT_CONSTS(for (int k_ = t; k_ < kMaxOut; k_ += T) sBo[k_] = k_ < a.c ? a.bo[k_] : 0.f;)
         }
     }
     const float* set = tp.qkv(l & 1);
@@ -195,47 +169,8 @@ __global__ __launch_bounds__(kWaves * 64) void grid_sigmoid_forward_kernel(const
         tp.DEN[static_cast<size_t>(l) * n + i] = static_cast<float>(den);
         store_row<DP>(tp.att_lo() + (static_cast<size_t>(l) * n + i) * DP, lo);
     }
-    store_row<DP>(tp.ATT + (static_cast<size_t>(l) * n + i) * DP, att);
     float out[DP];
-    if (a.use_graph) {
-        float g[DP];
-#pragma unroll
-        for (int m = 0; m < DP; ++m) g[m] = 0.f;
-        const int e1 = a.rowptr[i + 1];
-        for (int e = a.rowptr[i]; e < e1; ++e) {                                      // :75-78, entries in edge order
-            const float wgt = a.val[e];
-            float vr[DP];
-            load_row<DP>(Vl + static_cast<size_t>(a.nbr[e]) * DP, vr);
-#pragma unroll
-            for (int m = 0; m < DP; ++m) g[m] += wgt * vr[m];
-        }
-#pragma unroll
-        for (int m = 0; m < DP; ++m) out[m] = a.a_s * att[m] + a.g_s * g[m];          // :130-134
-    } else {
-#pragma unroll
-        for (int m = 0; m < DP; ++m) out[m] = att[m];
-    }
-    float h[DP];
-    load_row<DP>(tp.H + (static_cast<size_t>(l) * n + i) * DP, h);
-    if (a.use_source) {                                                               // :139-140
-        float x0[DP];
-        load_row<DP>(tp.H + static_cast<size_t>(i) * DP, x0);
-#pragma unroll
-        for (int m = 0; m < DP; ++m) out[m] += x0[m];
-    }
-    if (a.residual) {                                                                 // :200-201
-#pragma unroll
-        for (int m = 0; m < DP; ++m) out[m] = a.alpha * out[m] + (1.0f - a.alpha) * h[m];
-    }
-    store_row<DP>(tp.Z + (static_cast<size_t>(l + 1) * n + i) * DP, out);
-    if (a.use_bn) {                                                                   // :202-203
-        float mean, rstd;
-        ln_stats<DP>(out, d, a.eps, mean, rstd);
-#pragma unroll
-        for (int m = 0; m < DP; ++m) out[m] = (m < d) ? (out[m] - mean) * rstd * sL.lnw[m] + sL.lnb[m] : 0.f;
-    }
-    if (drop) dropout_row<DP>(out, a.rnd, (static_cast<int64_t>(l + 1) * n + i) * d, d, a.p_drop);   // :204
-    store_row<DP>(tp.H + (static_cast<size_t>(l + 1) * n + i) * DP, out);
+    TINY_LAYER_TAIL_FORWARD(Vl, tp.H + (static_cast<size_t>(l) * n + i) * DP, sL, l, i, att, out)
     if (!last) {
         float q[DP], k[DP], v[DP];
         project<DP>(sNext, a.use_weight, out, q, k, v);
@@ -244,12 +179,7 @@ __global__ __launch_bounds__(kWaves * 64) void grid_sigmoid_forward_kernel(const
         store_row<DP>(nxt + nd + static_cast<size_t>(i) * DP, k);
         store_row<DP>(nxt + 2 * nd + static_cast<size_t>(i) * DP, v);
     } else {
-        for (int c = 0; c < a.c; ++c) {                                               // :208
-            float acc = sBo[c];
-#pragma unroll
-            for (int m = 0; m < DP; ++m) acc += sWo[c * DP + m] * out[m];
-            a.y[static_cast<size_t>(i) * a.c + c] = acc;
-        }
+        TINY_OUTPUT_ROW(i, out)                                               // :208
     }
 }
 
@@ -306,10 +236,7 @@ __global__ __launch_bounds__(kWaves * 64) void grid_sigmoid_backward_kernel(cons
     const float keep = drop ? 1.0f / (1.0f - a.p_drop) : 1.0f;
 
     if (stage == 0) {
-        for (int k = t; k < kMaxOut * DP; k += T) {
-            const int c = k / DP, m = k % DP;
-            sWo[k] = (c < a.c && m < d) ? a.wo[c * d + m] : 0.f;
-        }
+        TINY_LOAD_OUTPUT_CONSTS()
         load_layer<DP>(sPrev, a.lp[L - 1], d, a.use_weight, a.use_bn);
         __syncthreads();
         if (!live || t >= 64) return;
@@ -317,11 +244,7 @@ __global__ __launch_bounds__(kWaves * 64) void grid_sigmoid_backward_kernel(cons
 #pragma unroll
         for (int m = 0; m < DP; ++m) g[m] = 0.f;
         if (a.use_source) store_row<DP>(gs.DX0 + at_i, g);
-        for (int c = 0; c < a.c; ++c) {
-            const float gv = a.gy[static_cast<size_t>(i) * a.c + c];
-#pragma unroll
-            for (int m = 0; m < DP; ++m) g[m] += gv * sWo[c * DP + m];
-        }
+        TINY_OUTPUT_BACKWARD_ROW(i, g)
         tail_backward<DP>(a, tp, gs, sPrev, L - 1, i, g, drop, keep);
         return;
     }
@@ -331,14 +254,7 @@ __global__ __launch_bounds__(kWaves * 64) void grid_sigmoid_backward_kernel(cons
         load_layer<DP>(sL, a.lp[l], d, a.use_weight, a.use_bn);
         if (l > 0) load_layer<DP>(sPrev, a.lp[l - 1], d, a.use_weight, a.use_bn);
         else {
-            for (int k = t; k < DP * kMaxIn; k += T) {
-                const int m = k / kMaxIn, f = k % kMaxIn;
-                sW0[k] = (m < d && f < a.f_in) ? a.w0[m * a.f_in + f] : 0.f;
-            }
-            for (int k = t; k < DP; k += T) {
-                sLn0w[k] = (k < d && a.use_bn) ? a.ln0w[k] : 0.f;
-                sLn0b[k] = (k < d && a.use_bn) ? a.ln0b[k] : 0.f;
-            }
+            TINY_LOAD_INPUT_CONSTS()
         }
     }
     const int set = l & 1;
@@ -433,16 +349,9 @@ __global__ __launch_bounds__(kWaves * 64) void grid_sigmoid_backward_kernel(cons
             dv[m] = static_cast<float>(s[2 * DP + m]);
         }
     }
-    if (a.use_graph) {                              // adjoint of the aggregation: entries of the TRANSPOSED CSR, edge order
+    if (a.use_graph) {                              // adjoint of the aggregation: the TRANSPOSED CSR, edge order
         const float* SG = gs.in_set(set, kSG);
-        const int e1 = a.rowptr[i + 1];
-        for (int e = a.rowptr[i]; e < e1; ++e) {
-            const float wgt = a.val[e];
-            float gr[DP];
-            load_row<DP>(SG + static_cast<size_t>(a.nbr[e]) * DP, gr);
-#pragma unroll
-            for (int m = 0; m < DP; ++m) dv[m] += wgt * gr[m];
-        }
+        TINY_GATHER_ROWS(SG, i, dv)
     }
 #pragma unroll
     for (int m = 0; m < DP; ++m)
@@ -451,14 +360,7 @@ __global__ __launch_bounds__(kWaves * 64) void grid_sigmoid_backward_kernel(cons
     store_row<DP>(gs.per_layer(l, kDK) + at_i, dk);
     store_row<DP>(gs.per_layer(l, kDV) + at_i, dv);
     float dh[DP];
-    load_row<DP>(gs.DIR + at_i, dh);
-    matvec_t_add<DP>(sL.wq, dq, dh);
-    matvec_t_add<DP>(sL.wk, dk, dh);
-    if (a.use_weight) matvec_t_add<DP>(sL.wv, dv, dh);
-    else {
-#pragma unroll
-        for (int m = 0; m < DP; ++m) dh[m] += dv[m];
-    }
+    TINY_BACK_PROJECT(gs.DIR + at_i, sL, dq, dk, dv, dh)
     if (l > 0) {
         tail_backward<DP>(a, tp, gs, sPrev, l - 1, i, dh, drop, keep);
         return;

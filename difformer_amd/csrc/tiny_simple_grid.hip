@@ -10,7 +10,10 @@
 //     forward   L + 1 launches:  [input layer, projections 0, sums 0] , [attention l, aggregation, tail, projections l + 1, sums l + 1 | output] x L
 //     backward  L + 2 launches:  [output Linear, tail L-1, attention set-up, sums] , [attention l, projections l, tail l - 1 ... | input layer] x L ,
 //                                [every parameter gradient: tiny::grid_sums]
-// Same arithmetic as the one-workgroup kernel (closed form of the attention and of its backward), same tape, scratch and C calls.
+// Same tape, scratch and C calls as the one-workgroup kernel, and the same arithmetic from the same text: the per-node stages
+// (the attention's closed form and its backward's set-up among them) are the TINY_* macros of tiny_stages.h, run on this plan's
+// scratch layout by tail_backward_common / input_backward of tiny_grid.h.  Here: the block shares of the sums over nodes, the second
+// half of the attention's backward and the launch sequences.
 #include "tiny_grid.h"
 
 using namespace tiny;
@@ -68,37 +71,11 @@ __global__ __launch_bounds__(kThreads) void grid_simple_forward_kernel(const Tin
     int next_set = 0;
 
     if (stage == 0) {
-        for (int kk = t; kk < DP * kMaxIn; kk += T) {
-            const int m = kk / kMaxIn, f = kk % kMaxIn;
-            sW0[kk] = (m < d && f < a.f_in) ? a.w0[m * a.f_in + f] : 0.f;
-        }
-        for (int kk = t; kk < DP; kk += T) {
-            sB0[kk] = kk < d ? a.b0[kk] : 0.f;
-            sLn0w[kk] = (kk < d && a.use_bn) ? a.ln0w[kk] : 0.f;
-            sLn0b[kk] = (kk < d && a.use_bn) ? a.ln0b[kk] : 0.f;
-        }
+        TINY_LOAD_INPUT_CONSTS(sB0[k_] = k_ < d ? a.b0[k_] : 0.f;)
         load_layer<DP>(sNext, a.lp[0], d, a.use_weight, a.use_bn);
         __syncthreads();
         if (live) {                                                        // input layer (:188-192)
-#pragma unroll
-            for (int m = 0; m < DP; ++m) h[m] = sB0[m];
-            const float* xr = a.x + i * a.ldx;
-            for (int f = 0; f < a.f_in; ++f) {
-                const float xv = xr[f];
-#pragma unroll
-                for (int m = 0; m < DP; ++m) h[m] += sW0[m * kMaxIn + f] * xv;
-            }
-            store_row<DP>(tp.Z + static_cast<size_t>(i) * DP, h);
-            if (a.use_bn) {
-                float mean, rstd;
-                ln_stats<DP>(h, d, a.eps, mean, rstd);
-#pragma unroll
-                for (int m = 0; m < DP; ++m) h[m] = (m < d) ? (h[m] - mean) * rstd * sLn0w[m] + sLn0b[m] : 0.f;
-            }
-#pragma unroll
-            for (int m = 0; m < DP; ++m) h[m] = fmaxf(h[m], 0.f);
-            if (drop) dropout_row<DP>(h, a.rnd, static_cast<int64_t>(i) * d, d, a.p_drop);
-            store_row<DP>(tp.H + static_cast<size_t>(i) * DP, h);
+            TINY_INPUT_FORWARD(i, h)
         }
     } else {
         const int l = stage - 1;
@@ -106,11 +83,7 @@ __global__ __launch_bounds__(kThreads) void grid_simple_forward_kernel(const Tin
         load_layer<DP>(sL, a.lp[l], d, a.use_weight, a.use_bn);
         if (!last) load_layer<DP>(sNext, a.lp[l + 1], d, a.use_weight, a.use_bn);
         else {
-            for (int kk = t; kk < kMaxOut * DP; kk += T) {
-                const int c = kk / DP, m = kk % DP;
-                sWo[kk] = (c < a.c && m < d) ? a.wo[c * d + m] : 0.f;
-            }
-            for (int kk = t; kk < kMaxOut; kk += T) sBo[kk] = kk < a.c ? a.bo[kk] : 0.f;
+            TINY_LOAD_OUTPUT_CONSTS(for (int k_ = t; k_ < kMaxOut; k_ += T) sBo[k_] = k_ < a.c ? a.bo[k_] : 0.f;)
         }
         add_block_sums(shares + static_cast<size_t>(l & 1) * G * 96, G, fwd_sums<DP>(), sSum);      // (syncs)
         if (blockIdx.x == 0 && t < fwd_sums<DP>()) tp.SUM[l * 96 + t] = sSum[t];                      // the backward reads them
@@ -119,70 +92,14 @@ __global__ __launch_bounds__(kThreads) void grid_simple_forward_kernel(const Tin
         next_set = (l + 1) & 1;
         if (live) {
             load_row<DP>(set + static_cast<size_t>(i) * DP, q);
-            // :20-38  closed form of the attention from the layer's sums
-            const float q2 = sSum[DP * DP + 2 * DP], k2 = sSum[DP * DP + 2 * DP + 1];
-            const float s = 1.0f / (sqrtf(q2) * sqrtf(k2));
-            float den = 0.f, att[DP];
-#pragma unroll
-            for (int m = 0; m < DP; ++m) den += q[m] * sSum[DP * DP + m];
-            den = s * den + static_cast<float>(n);
-#pragma unroll
-            for (int dd = 0; dd < DP; ++dd) {
-                float num = 0.f;
-#pragma unroll
-                for (int m = 0; m < DP; ++m) num += q[m] * sSum[m * DP + dd];
-                att[dd] = (s * num + sSum[DP * DP + DP + dd]) / den;
-            }
-            store_row<DP>(tp.ATT + (static_cast<size_t>(l) * n + i) * DP, att);
+            float att[DP];
+            TINY_SIMPLE_ATTENTION_ROW(q, att)                         // :20-38  closed form of the attention from the layer's sums
             float out[DP];
-            if (a.use_graph) {
-                float g[DP];
-#pragma unroll
-                for (int m = 0; m < DP; ++m) g[m] = 0.f;
-                const int e1 = a.rowptr[i + 1];
-                for (int e = a.rowptr[i]; e < e1; ++e) {                              // :75-78, entries in edge order
-                    const float wgt = a.val[e];
-                    float vr[DP];
-                    load_row<DP>(Vl + static_cast<size_t>(a.nbr[e]) * DP, vr);
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) g[m] += wgt * vr[m];
-                }
-#pragma unroll
-                for (int m = 0; m < DP; ++m) out[m] = a.a_s * att[m] + a.g_s * g[m];  // :130-134
-            } else {
-#pragma unroll
-                for (int m = 0; m < DP; ++m) out[m] = att[m];
-            }
-            float hl[DP];
-            load_row<DP>(tp.H + (static_cast<size_t>(l) * n + i) * DP, hl);
-            if (a.use_source) {                                                       // :139-140
-                float x0[DP];
-                load_row<DP>(tp.H + static_cast<size_t>(i) * DP, x0);
-#pragma unroll
-                for (int m = 0; m < DP; ++m) out[m] += x0[m];
-            }
-            if (a.residual) {                                                         // :200-201
-#pragma unroll
-                for (int m = 0; m < DP; ++m) out[m] = a.alpha * out[m] + (1.0f - a.alpha) * hl[m];
-            }
-            store_row<DP>(tp.Z + (static_cast<size_t>(l + 1) * n + i) * DP, out);
-            if (a.use_bn) {                                                           // :202-203
-                float mean, rstd;
-                ln_stats<DP>(out, d, a.eps, mean, rstd);
-#pragma unroll
-                for (int m = 0; m < DP; ++m) out[m] = (m < d) ? (out[m] - mean) * rstd * sL.lnw[m] + sL.lnb[m] : 0.f;
-            }
-            if (drop) dropout_row<DP>(out, a.rnd, (static_cast<int64_t>(l + 1) * n + i) * d, d, a.p_drop);   // :204
-            store_row<DP>(tp.H + (static_cast<size_t>(l + 1) * n + i) * DP, out);
+            TINY_LAYER_TAIL_FORWARD(Vl, tp.H + (static_cast<size_t>(l) * n + i) * DP, sL, l, i, att, out)
 #pragma unroll
             for (int m = 0; m < DP; ++m) h[m] = out[m];
             if (last) {
-                for (int c = 0; c < a.c; ++c) {                                       // :208
-                    float acc = sBo[c];
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) acc += sWo[c * DP + m] * out[m];
-                    a.y[static_cast<size_t>(i) * a.c + c] = acc;
-                }
+                TINY_OUTPUT_ROW(i, out)                                               // :208
             }
         }
         if (last) return;
@@ -238,34 +155,8 @@ __device__ __forceinline__ void tail_backward(const TinyArgs& a, const Tape<DP>&
     tail_backward_common<DP>(a, tp, gs, w, l, i, dy, drop, keep, datt, q, k, v);
     const float q2 = sSum[DP * DP + 2 * DP], k2 = sSum[DP * DP + 2 * DP + 1];
     const float s = 1.0f / (sqrtf(q2) * sqrtf(k2));
-    float A[DP], b = 0.f;
-#pragma unroll
-    for (int dd = 0; dd < DP; ++dd) {
-        float acc = 0.f;
-#pragma unroll
-        for (int m = 0; m < DP; ++m) acc += q[m] * sSum[m * DP + dd];
-        A[dd] = acc;
-    }
-#pragma unroll
-    for (int m = 0; m < DP; ++m) b += q[m] * sSum[DP * DP + m];
-    const float den = s * b + static_cast<float>(n);
-    float dnum[DP], dden = 0.f, ts = 0.f;
-#pragma unroll
-    for (int dd = 0; dd < DP; ++dd) {
-        const float att = (s * A[dd] + sSum[DP * DP + DP + dd]) / den;
-        dnum[dd] = datt[dd] / den;
-        dden -= dnum[dd] * att;
-        ts += dnum[dd] * A[dd];
-    }
-    ts += dden * b;
-    float dq[DP];
-#pragma unroll
-    for (int m = 0; m < DP; ++m) {
-        float acc = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < DP; ++dd) acc += sSum[m * DP + dd] * dnum[dd];
-        dq[m] = s * (acc + dden * sSum[DP * DP + m]);
-    }
+    float dnum[DP], dden = 0.f, ts = 0.f, dq[DP];
+    TINY_SIMPLE_BACKWARD_SETUP(q, datt, s, dnum, dden, ts, dq)
     store_row<DP>(gs.per_layer(l, kDQ) + at_i, dq);            // completed by the next launch (+ 2 g_q2 q)
 #pragma unroll
     for (int m = 0; m < DP; ++m) { row[m] = q[m]; row[DP + m] = dnum[m]; }
@@ -298,10 +189,7 @@ __global__ __launch_bounds__(kThreads) void grid_simple_backward_kernel(const Ti
 
     if (stage == 0) {
         lp = L - 1;
-        for (int kk = t; kk < kMaxOut * DP; kk += T) {
-            const int c = kk / DP, m = kk % DP;
-            sWo[kk] = (c < a.c && m < d) ? a.wo[c * d + m] : 0.f;
-        }
+        TINY_LOAD_OUTPUT_CONSTS()
         load_layer<DP>(sPrev, a.lp[lp], d, a.use_weight, a.use_bn);
         for (int kk = t; kk < fwd_sums<DP>(); kk += T) sSumPrev[kk] = tp.SUM[lp * 96 + kk];
         __syncthreads();
@@ -310,11 +198,7 @@ __global__ __launch_bounds__(kThreads) void grid_simple_backward_kernel(const Ti
 #pragma unroll
             for (int m = 0; m < DP; ++m) g[m] = 0.f;
             if (a.use_source) store_row<DP>(gs.DX0 + at_i, g);
-            for (int c = 0; c < a.c; ++c) {
-                const float gv = a.gy[static_cast<size_t>(i) * a.c + c];
-#pragma unroll
-                for (int m = 0; m < DP; ++m) g[m] += gv * sWo[c * DP + m];
-            }
+            TINY_OUTPUT_BACKWARD_ROW(i, g)
             tail_backward<DP>(a, tp, gs, sPrev, sSumPrev, lp, i, g, drop, keep, row);
         }
     } else {
@@ -326,14 +210,7 @@ __global__ __launch_bounds__(kThreads) void grid_simple_backward_kernel(const Ti
             load_layer<DP>(sPrev, a.lp[lp], d, a.use_weight, a.use_bn);
             for (int kk = t; kk < fwd_sums<DP>(); kk += T) sSumPrev[kk] = tp.SUM[lp * 96 + kk];
         } else {
-            for (int kk = t; kk < DP * kMaxIn; kk += T) {
-                const int m = kk / kMaxIn, f = kk % kMaxIn;
-                sW0[kk] = (m < d && f < a.f_in) ? a.w0[m * a.f_in + f] : 0.f;
-            }
-            for (int kk = t; kk < DP; kk += T) {
-                sLn0w[kk] = (kk < d && a.use_bn) ? a.ln0w[kk] : 0.f;
-                sLn0b[kk] = (kk < d && a.use_bn) ? a.ln0b[kk] : 0.f;
-            }
+            TINY_LOAD_INPUT_CONSTS()
         }
         add_block_sums(shares + static_cast<size_t>(l & 1) * G * 96, G, bwd_sums<DP>(), sG);       // (syncs)
         const int set = l & 1;
@@ -363,16 +240,9 @@ __global__ __launch_bounds__(kThreads) void grid_simple_backward_kernel(const Ti
                 for (int m = 0; m < DP; ++m) acc += sG[m * DP + dd] * k[m];
                 dv[dd] = acc + sG[DP * DP + DP + dd];
             }
-            if (a.use_graph) {                      // adjoint of the aggregation: entries of the TRANSPOSED CSR, edge order
+            if (a.use_graph) {                              // adjoint of the aggregation: the TRANSPOSED CSR, edge order
                 const float* SG = gs.in_set(set, kSG);
-                const int e1 = a.rowptr[i + 1];
-                for (int e = a.rowptr[i]; e < e1; ++e) {
-                    const float wgt = a.val[e];
-                    float gr[DP];
-                    load_row<DP>(SG + static_cast<size_t>(a.nbr[e]) * DP, gr);
-#pragma unroll
-                    for (int m = 0; m < DP; ++m) dv[m] += wgt * gr[m];
-                }
+                TINY_GATHER_ROWS(SG, i, dv)
             }
 #pragma unroll
             for (int m = 0; m < DP; ++m)
@@ -381,14 +251,7 @@ __global__ __launch_bounds__(kThreads) void grid_simple_backward_kernel(const Ti
             store_row<DP>(gs.per_layer(l, kDK) + at_i, dk);
             store_row<DP>(gs.per_layer(l, kDV) + at_i, dv);
             float dh[DP];
-            load_row<DP>(gs.DIR + at_i, dh);
-            matvec_t_add<DP>(sL.wq, dq, dh);
-            matvec_t_add<DP>(sL.wk, dk, dh);
-            if (a.use_weight) matvec_t_add<DP>(sL.wv, dv, dh);
-            else {
-#pragma unroll
-                for (int m = 0; m < DP; ++m) dh[m] += dv[m];
-            }
+            TINY_BACK_PROJECT(gs.DIR + at_i, sL, dq, dk, dv, dh)
             if (l > 0) tail_backward<DP>(a, tp, gs, sPrev, sSumPrev, lp, i, dh, drop, keep, row);
             else input_backward<DP>(a, tp, gs, sW0, sLn0w, sLn0b, i, dh, drop, keep);
         }
