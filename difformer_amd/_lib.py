@@ -37,6 +37,9 @@ ADAM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "diffor
 # the graph read-out library (C ABI: include/difformer_readout.h), loaded on first use by load_readout()
 READOUT_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_readout.so")
 READOUT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_readout.h"))
+# the batched neighbour-graph library (C ABI: include/difformer_nbr.h), loaded on first use by load_nbr()
+NBR_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_nbr.so")
+NBR_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_nbr.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -176,6 +179,12 @@ READOUT_VERSION = _defines(_readout_code, "DIF_READOUT_VERSION")["DIF_READOUT_VE
 READOUT_CONSTANTS = _defines(_readout_code, r"DIF_READOUT_(?:ADD|MEAN|MAX|MAX_COLUMNS)")      # mode codes, the column limit
 READOUT_SIGNATURES = _prototypes(_readout_code)
 
+# ... and include/difformer_nbr.h of the tenth's
+_nbr_code = _read_header(NBR_HEADER_PATH)
+NBR_VERSION = _defines(_nbr_code, "DIF_NBR_VERSION")["DIF_NBR_VERSION"]
+NBR_CONSTANTS = _defines(_nbr_code, r"DIF_NBR_MAX_(?:COLUMNS|K|CAP)")      # the limits of the batched kernels
+NBR_SIGNATURES = _prototypes(_nbr_code)
+
 _lib = None
 _maps = None
 _edges = None
@@ -185,6 +194,7 @@ _metrics = None
 _loss = None
 _adam = None
 _readout = None
+_nbr = None
 
 
 class DifformerHipError(RuntimeError):
@@ -319,6 +329,14 @@ def load_readout():
     return _readout
 
 
+def load_nbr():
+    """Load libdifformer_nbr.so once."""
+    global _nbr
+    if _nbr is None:
+        _nbr = _load_side(NBR_LIB_PATH, NBR_SIGNATURES, "dif_nbr_version", NBR_VERSION)
+    return _nbr
+
+
 def check_maps(rc, what):
     """check() for a call into libdifformer_maps.so: the message comes from that library."""
     if rc != 0:
@@ -372,6 +390,13 @@ def check_readout(rc, what):
     """check() for a call into libdifformer_readout.so: the message comes from that library."""
     if rc != 0:
         msg = load_readout().dif_readout_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
+
+
+def check_nbr(rc, what):
+    """check() for a call into libdifformer_nbr.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_nbr().dif_nbr_last_error()
         raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 

@@ -231,20 +231,21 @@ class HipBackend:
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in (self.kernel_events or {}).items()}
 
     def _call(self, label, symbol, dev, *args, maps=False, edges=False, knn=False, slots=False, metrics=False, loss=False,
-              adam=False, readout=False):
+              adam=False, readout=False, nbr=False):
         """Every launch goes through here: `symbol` of the C ABI with `args` and, last, torch's current stream on `dev`;
         a non-zero return raises DifformerHipError naming the symbol.  `label` is the key of the call's events in
         `kernel_events` (usually a family of symbols: bench.py and the tests key on it).  The common case -- no event
         collection, operands on the current device -- adds nothing around the call.  maps / edges / knn / slots / metrics /
-        loss / adam / readout: `symbol` is one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so
+        loss / adam / readout / nbr: `symbol` is one of libdifformer_maps.so (include/difformer_maps.h) / libdifformer_edges.so
         (include/difformer_edges.h) / libdifformer_knn.so (include/difformer_knn.h) / libdifformer_slots.so
         (include/difformer_slots.h) / libdifformer_metrics.so (include/difformer_metrics.h) / libdifformer_loss.so
         (include/difformer_loss.h) / libdifformer_adam.so (include/difformer_adam.h) / libdifformer_readout.so
-        (include/difformer_readout.h), loaded on first use."""
+        (include/difformer_readout.h) / libdifformer_nbr.so (include/difformer_nbr.h), loaded on first use."""
         side = ((_lib.load_maps, _lib.check_maps) if maps else (_lib.load_edges, _lib.check_edges) if edges else
                 (_lib.load_knn, _lib.check_knn) if knn else (_lib.load_slots, _lib.check_slots) if slots else
                 (_lib.load_metrics, _lib.check_metrics) if metrics else (_lib.load_loss, _lib.check_loss) if loss else
-                (_lib.load_adam, _lib.check_adam) if adam else (_lib.load_readout, _lib.check_readout) if readout else None)
+                (_lib.load_adam, _lib.check_adam) if adam else (_lib.load_readout, _lib.check_readout) if readout else
+                (_lib.load_nbr, _lib.check_nbr) if nbr else None)
         fn = getattr(side[0]() if side else self.lib, symbol)
         index = dev.index
         if self.kernel_events is None and index is not None and torch.cuda.current_device() == index:
@@ -427,6 +428,63 @@ class HipBackend:
         ws = _workspace(ws_bytes, dev, floor=16)
         self._call("dif_knn_graph_f32", "dif_knn_graph_f32", dev, _ptr(x), ldx, N, M, int(k), int(bool(loop)), int(metric),
                    int(centre_row), int(route), _ptr(edge_index), _ptr(dist), _ptr(ws), ws_bytes, knn=True)
+        return edge_index, dist
+
+    # ---- neighbour graphs of a batch (libdifformer_nbr.so) -----------------------------------------
+    @staticmethod
+    def _nbr_operands(who, x, graph_ptr):
+        dev = _require_device(x, graph_ptr)
+        _all_f32(x=x)
+        N, M = x.shape
+        ldx = int(x.stride(0)) if N > 1 else M
+        if x.stride(1) != 1 or ldx < M or ldx % 4 or x.data_ptr() % 16:
+            raise ValueError(f"difformer_amd: {who} takes rows of unit column stride on 16-byte boundaries "
+                             f"(got strides {tuple(x.stride())}, address % 16 = {x.data_ptr() % 16})")
+        if graph_ptr.dtype != torch.int32 or graph_ptr.dim() != 1 or graph_ptr.shape[0] < 2 or not graph_ptr.is_contiguous():
+            raise ValueError(f"difformer_amd: {who} takes graph_ptr as a contiguous int32 [B + 1] (got {graph_ptr.dtype}, "
+                             f"{tuple(graph_ptr.shape)})")
+        return dev, N, M, ldx, graph_ptr.shape[0] - 1
+
+    def nbr_knn(self, x, graph_ptr, edge_ptr, E, k, loop, metric, centre_row, want_dist=False):
+        """x [N,M] float32, M a multiple of 4 up to 64; graph_ptr int32 [B + 1] as ops.BatchLayout makes it; edge_ptr int64
+        [B + 1], edge_ptr[b] = sum over b' < b of n_b' kk_b' with kk_b = min(k, n_b - (0 if loop else 1)), edge_ptr[B] == E (the
+        caller, neighbors.py, knows E on the host) -> (edge_index int64 [2, E], dist float32 [E] or None): per row its kk_b
+        nearest rows of its own graph, nearest first, as `knn_graph` ranks them (csrc/nbr_batched.hip)."""
+        dev, N, M, ldx, B = self._nbr_operands("nbr_knn", x, graph_ptr)
+        if edge_ptr.dtype != torch.int64 or tuple(edge_ptr.shape) != (B + 1,) or edge_ptr.device != dev or not edge_ptr.is_contiguous():
+            raise ValueError(f"difformer_amd: nbr_knn takes edge_ptr as a contiguous int64 [{B + 1}] on {dev}")
+        E = int(E)
+        edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
+        dist = torch.empty(E, dtype=torch.float32, device=dev) if want_dist else None
+        self._call("dif_nbr_knn_f32", "dif_nbr_knn_f32", dev, _ptr(x), ldx, N, M, _ptr(graph_ptr), _ptr(edge_ptr), B, int(k),
+                   int(bool(loop)), int(metric), int(centre_row), _ptr(edge_index) if E else None, E,
+                   _ptr(dist) if E else None, nbr=True)
+        return edge_index, dist
+
+    def nbr_radius_lists(self, x, graph_ptr, r, loop, cap):
+        """x, graph_ptr as nbr_knn -> (deg int32 [N], workspace): per row the number of rows of its own graph with squared
+        float64 distance < r r (strict; at most `cap`, the nearest kept) and, in the workspace, their ranked lists for
+        nbr_radius_edges (csrc/nbr_batched.hip)."""
+        dev, N, M, ldx, B = self._nbr_operands("nbr_radius_lists", x, graph_ptr)
+        nbr = _lib.load_nbr()
+        deg = torch.empty(N, dtype=torch.int32, device=dev)
+        ws_bytes = nbr.dif_nbr_workspace_bytes(N, int(cap))
+        ws = _workspace(ws_bytes, dev, floor=16)
+        self._call("dif_nbr_radius_lists_f32", "dif_nbr_radius_lists_f32", dev, _ptr(x), ldx, N, M, _ptr(graph_ptr), B, float(r),
+                   int(bool(loop)), int(cap), _ptr(deg), _ptr(ws), ws_bytes, nbr=True)
+        return deg, ws
+
+    def nbr_radius_edges(self, deg_ptr, E, cap, centre_row, ws, want_dist=False):
+        """deg_ptr int64 [N + 1], the exclusive prefix sum of nbr_radius_lists' deg with deg_ptr[N] == E, and its workspace ->
+        (edge_index int64 [2, E], dist float32 [E] or None): centres ascending, nearest first."""
+        dev = _require_device(deg_ptr, ws)
+        if deg_ptr.dtype != torch.int64 or deg_ptr.dim() != 1 or deg_ptr.shape[0] < 2 or not deg_ptr.is_contiguous():
+            raise ValueError("difformer_amd: nbr_radius_edges takes deg_ptr as a contiguous int64 [N + 1]")
+        N, E = deg_ptr.shape[0] - 1, int(E)
+        edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
+        dist = torch.empty(E, dtype=torch.float32, device=dev) if want_dist else None
+        self._call("dif_nbr_radius_edges", "dif_nbr_radius_edges", dev, _ptr(deg_ptr), N, int(cap), int(centre_row), _ptr(ws),
+                   ws.numel(), _ptr(edge_index) if E else None, E, _ptr(dist) if E else None, nbr=True)
         return edge_index, dist
 
     # ---- evaluation metrics (libdifformer_metrics.so) ---------------------------------------------

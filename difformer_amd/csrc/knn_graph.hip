@@ -27,6 +27,7 @@
 #include <stdarg.h>
 #include "dif_common.h"
 #include "topk_select.h"
+#include "knn_order.h"
 #include "../../include/difformer_knn.h"
 
 // dif::launch (csrc/dif_launch.h) reports through these; api.hip defines them for libdifformer_hip.so, this file for THIS
@@ -57,6 +58,7 @@ namespace {
 using dif::f32x4;
 using dif::ld4;
 using dif::candidate, dif::fold, dif::insert, dif::key_score;
+using dif::kEmpty, dif::kNaNKey, dif::dist_key, dif::key_dist, dif::rnorm, dif::cos_dist, dif::insert2;
 
 constexpr int kMaxK = 24;
 constexpr int kMaxM = 512;
@@ -68,44 +70,7 @@ constexpr int kMaxSplits = 32;
 constexpr int kMinTilesPerSplit = 4;   // sweep: a key range holds at least this many 16-key tiles
 constexpr int64_t kFillWaves = 2 * 4 * dif::kCUs;     // two waves on each of the chip's SIMDs
 
-// ---- the float64 order -------------------------------------------------------------------------------------------------------
-constexpr uint64_t kEmpty = ~0ull;           // above every key: the empty slot of a list sorted ascending
-constexpr uint64_t kNaNKey = ~0ull - 1;      // a NaN distance: after every number (+inf is 0xFFF0...0), before the empty slot
-
-// distance -> unsigned key, monotone: a < b  <=>  key(a) < key(b); -0 and +0 share one key
-__device__ __forceinline__ uint64_t dist_key(double d) {
-    d += 0.0;
-    const uint64_t b = __builtin_bit_cast(uint64_t, d);
-    const uint64_t key = b ^ (static_cast<uint64_t>(static_cast<int64_t>(b) >> 63) | 0x8000000000000000ull);
-    return d != d ? kNaNKey : key;
-}
-__device__ __forceinline__ double key_dist(uint64_t key) {      // kNaNKey and kEmpty -> a NaN
-    const uint64_t b = (key & 0x8000000000000000ull) ? key ^ 0x8000000000000000ull : ~key;
-    return __builtin_bit_cast(double, b);
-}
-
-// 1 / |x| from |x|^2; a zero row has cosine 0 with every row (a NaN stays a NaN)
-__device__ __forceinline__ double rnorm(double n2) { return n2 == 0.0 ? 0.0 : 1.0 / sqrt(n2); }
-// 1 - (x_i . x_j) / (|x_i| |x_j|), the same three operations in both routes
-__device__ __forceinline__ double cos_dist(double dot, double ri, double rj) { return fma(-(dot * ri), rj, 1.0); }
-
-// (key, index) enters a list sorted ascending by key; strict comparisons: an equal key stays behind what is there already
-template <int K>
-__device__ __forceinline__ void insert2(uint64_t (&dk)[K], uint32_t (&ix)[K], uint64_t key, uint32_t index) {
-    dk[K - 1] = key;
-    ix[K - 1] = index;
-#pragma unroll
-    for (int i = K - 1; i > 0; --i) {
-        const bool up = dk[i] < dk[i - 1];
-        const uint64_t ka = dk[i - 1], kb = dk[i];
-        const uint32_t ia = ix[i - 1], ib = ix[i];
-        dk[i - 1] = up ? kb : ka;
-        dk[i] = up ? ka : kb;
-        ix[i - 1] = up ? ib : ia;
-        ix[i] = up ? ia : ib;
-    }
-}
-
+// ---- the float64 order: csrc/knn_order.h (shared with csrc/nbr_batched.hip) ---------------------------------------------------
 // the first kk entries of row i's list -> edge_index [2][E] (row `centre_row` holds i) and dist [E]
 template <int K, bool COS>
 __device__ __forceinline__ void write_row(const uint64_t (&dk)[K], const uint32_t (&ix)[K], int64_t i, int kk, int centre_row,

@@ -999,7 +999,7 @@ class BatchLayout:
             raise ValueError("difformer_amd: negative entry in n_nodes")
         if total >= 2 ** 31:
             raise ValueError("difformer_amd: batches are limited to 2^31 - 1 nodes")
-        self.n_rows, self.max_nodes = total, biggest
+        self.n_rows, self.max_nodes, self.min_nodes = total, biggest, smallest
         self.graph_ptr = ptr.to(torch.int32)
         order = torch.argsort(n, descending=True, stable=True)
         self.ranked_first = ptr[:-1][order].to(torch.int32).contiguous()
