@@ -12,7 +12,8 @@ with batch= / n_nodes=, radius_graph), from lib/libdifformer_nbr.so (include/dif
 (include/difformer_metrics.h), the training losses (masked log-softmax NLL, BCE with logits) from lib/libdifformer_loss.so
 (include/difformer_loss.h), the Adam update of a whole model in one launch from lib/libdifformer_adam.so
 (include/difformer_adam.h), the graph read-out (global_add_pool / global_mean_pool / global_max_pool behind GraphGNN) from
-lib/libdifformer_readout.so (include/difformer_readout.h).  Importing this package does not load the library; the first operator
+lib/libdifformer_readout.so (include/difformer_readout.h), all snapshots of a spatial-temporal epoch in one launch per pass
+(SnapshotBatch, DIFFormer.forward_snapshots) from lib/libdifformer_snapshots.so (include/difformer_snapshots.h).  Importing this package does not load the library; the first operator
 call does, and fails loudly if it has not been built.
 """
 from .attention_maps import attention_on_edges, attention_topk  # noqa: F401
@@ -25,9 +26,11 @@ from .metrics import eval_acc, eval_f1, eval_rocauc, rocauc_counts  # noqa: F401
 from .neighbors import kneighbors_graph, knn_graph, radius_graph  # noqa: F401
 from .optim import Adam  # noqa: F401
 from .readout import GraphGNN, global_add_pool, global_max_pool, global_mean_pool  # noqa: F401
+from .snapshots import SnapshotBatch  # noqa: F401
 
 __all__ = ["DIFFormer", "DIFFormerConv", "full_attention_conv", "gcn_conv", "DIFFormer_v2", "TransConv", "RowShard",
            "GraphedForward", "GraphedTrainStep", "graphed_training", "attention_topk", "attention_on_edges", "knn_graph",
            "kneighbors_graph", "radius_graph", "eval_rocauc", "eval_acc", "eval_f1", "rocauc_counts", "log_softmax_nll",
-           "bce_with_logits", "loss_record", "Adam", "global_add_pool", "global_mean_pool", "global_max_pool", "GraphGNN"]
+           "bce_with_logits", "loss_record", "Adam", "global_add_pool", "global_mean_pool", "global_max_pool", "GraphGNN",
+           "SnapshotBatch"]
 __version__ = "0.1.0"

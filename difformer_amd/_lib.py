@@ -40,6 +40,9 @@ READOUT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "dif
 # the batched neighbour-graph library (C ABI: include/difformer_nbr.h), loaded on first use by load_nbr()
 NBR_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_nbr.so")
 NBR_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_nbr.h"))
+# the snapshot-batch library (C ABI: include/difformer_snapshots.h), loaded on first use by load_snapshots()
+SNAPSHOTS_LIB_PATH = os.path.join(_HERE, "lib", "libdifformer_snapshots.so")
+SNAPSHOTS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "difformer_snapshots.h"))
 
 # The closed set of types the C ABI uses.  Every pointer is a c_void_p (device addresses arrive as integers), except the
 # configuration struct; anything else in the header is an error, never a guess.
@@ -185,6 +188,12 @@ NBR_VERSION = _defines(_nbr_code, "DIF_NBR_VERSION")["DIF_NBR_VERSION"]
 NBR_CONSTANTS = _defines(_nbr_code, r"DIF_NBR_MAX_(?:COLUMNS|K|CAP)")      # the limits of the batched kernels
 NBR_SIGNATURES = _prototypes(_nbr_code)
 
+# ... and include/difformer_snapshots.h of the eleventh's
+_snapshots_code = _read_header(SNAPSHOTS_HEADER_PATH)
+SNAPSHOTS_VERSION = _defines(_snapshots_code, "DIF_SNAP_VERSION")["DIF_SNAP_VERSION"]
+SNAPSHOTS_CONSTANTS = _defines(_snapshots_code, r"DIF_SNAP_RECORD_FIELDS")      # int64 words of a snapshot record
+SNAPSHOTS_SIGNATURES = _prototypes(_snapshots_code)
+
 _lib = None
 _maps = None
 _edges = None
@@ -195,6 +204,7 @@ _loss = None
 _adam = None
 _readout = None
 _nbr = None
+_snapshots = None
 
 
 class DifformerHipError(RuntimeError):
@@ -337,6 +347,14 @@ def load_nbr():
     return _nbr
 
 
+def load_snapshots():
+    """Load libdifformer_snapshots.so once."""
+    global _snapshots
+    if _snapshots is None:
+        _snapshots = _load_side(SNAPSHOTS_LIB_PATH, SNAPSHOTS_SIGNATURES, "dif_snap_version", SNAPSHOTS_VERSION)
+    return _snapshots
+
+
 def check_maps(rc, what):
     """check() for a call into libdifformer_maps.so: the message comes from that library."""
     if rc != 0:
@@ -397,6 +415,13 @@ def check_nbr(rc, what):
     """check() for a call into libdifformer_nbr.so: the message comes from that library."""
     if rc != 0:
         msg = load_nbr().dif_nbr_last_error()
+        raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
+
+
+def check_snapshots(rc, what):
+    """check() for a call into libdifformer_snapshots.so: the message comes from that library."""
+    if rc != 0:
+        msg = load_snapshots().dif_snap_last_error()
         raise DifformerHipError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}", rc)
 
 

@@ -614,6 +614,12 @@ class DIFFormer(nn.Module):
         out = self._forward_graphed(x, edge_index, edge_weight)
         return out if out is not None else self._forward_eager(x, edge_index, edge_weight)
 
+    def forward_snapshots(self, batch, *, _uniforms=None):
+        """The rows of `self(x_b, edge_index_b, edge_weight_b)` for every snapshot b of a `SnapshotBatch`, stacked: on tiny graphs
+        ONE launch of one workgroup per snapshot and ONE autograd node (difformer_amd/snapshots.py); a plain loop otherwise."""
+        from . import snapshots
+        return snapshots.forward_snapshots(self, batch, _uniforms=_uniforms)
+
     def _forward_eager(self, x, edge_index, edge_weight=None):
         layer_ = []
         # A graph with community structure (every row's entries in one or two source tiles) runs in a mixed node order:
